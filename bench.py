@@ -58,7 +58,52 @@ def parse():
     ap.add_argument('--host-input-steps', type=int, default=100,
                     help='extra leg on rank 0 at N=1: steps fed from uint8 frames in host memory through the PCIe feeder '
                          '(reported as pcie_inclusive, never as value; 0 = skip)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy, float32 / '
+                         'float64, at most 64 MB in all: see step_outputs()')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def step_outputs(ts, out):
+    """What the last step() left its caller, copied to the host: the returned [elbo, err, kl, beta used] (step_out), the
+    model's state_dict -- parameters and buffers the step updated in place (state.<key>) --, the Adam first moments, i.e. the
+    running mean of the gradients the step consumed (adam_exp_avg.<parameter>), and the GECO state (geco_state)."""
+    arrays = {'step_out': out}
+    if ts.geco is not None:
+        arrays['geco_state'] = ts.geco.state
+    for k, v in ts.model.state_dict().items():
+        arrays['state.' + k] = v
+    if ts.optimiser == 'adam':
+        for k, p in ts.model.named_parameters():
+            arrays['adam_exp_avg.' + k] = ts._adam_slices(p)[0]
+    return {k: (v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float()).detach().cpu().numpy()
+            for k, v in arrays.items()}
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays -> path/<name>.npy.  If they exceed `limit` bytes together, every array keeps the same fraction of its elements:
+    a sorted sample drawn with a fixed seed (the same positions for the same shapes, run after run), flattened."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, (limit - 256 * len(arrays)) / float(max(total, 1)))      # (256 bytes: a .npy header)
+    sampled, written = [], 0
+    for name, a in arrays.items():
+        keep = int(a.size * frac)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(path, name + '.npy'), a)
+        written += os.path.getsize(os.path.join(path, name + '.npy'))
+    return {'dir': path, 'arrays': len(arrays), 'bytes': written, 'sampled': sampled,
+            'sample': 'sorted positions from numpy.random.default_rng(0).choice(size, keep, replace=False), flattened' if sampled else None}
 
 
 def build_model(args, device):
@@ -306,6 +351,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # (the legs below step the same model on: what the last timed step computed is copied out now, outside the timed region)
+    dumped = step_outputs(ts, out) if args.dump_outputs and rank == 0 else None
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -433,6 +480,9 @@ def main():
                                                                    'over ranks); inside the step the collective is not overlapped'}
         if flop_img:
             result['step_fraction_of_fp32_mfma_peak'] = value / world * flop_img / (PEAK_FP32_MFMA_TFLOPS * 1e12)
+        if dumped is not None:
+            result['dumped_outputs'] = dump_outputs(args.dump_outputs, dumped)
+            del dumped
 
     # ---- roofline leg: HIP events around every kernel launch, eager steps, same process (rank 0)
     if rank == 0 and args.profile_steps > 0 and world == 1:

@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: load a golden fixture, rebuild its closed-form
 weights / inputs / noise, and compare a forward result against it."""
+import collections
 import json
 import os.path as osp
 
@@ -104,6 +105,15 @@ class Golden(object):
             floor = (2e-5 + 1e-6 * big) * np.sqrt(len(ref) / max(1, int(s['n'])))
             assert diff <= l2_tol * np.linalg.norm(ref) + floor, \
                 '%s grad %s: sample rel-L2 %.3e' % (self.name, name, diff / (np.linalg.norm(ref) + 1e-30))
+
+
+def load_live_recording(name):
+    """tests/golden/live_<name>.npz (tests/golden/make_golden_live.py): the reference run of a live-import check as it was
+    recorded from the import -- (the reference's state_dict as formula_state_dict reads it, input, {output name: tensor})."""
+    g = np.load(osp.join(GOLDEN, 'live_%s.npz' % name), allow_pickle=False)
+    sd = collections.OrderedDict((str(k), torch.from_numpy(g['sd/%s' % k])) for k in g['sd_keys'])
+    outs = {k[len('out/'):]: torch.from_numpy(g[k]) for k in g.files if k.startswith('out/')}
+    return sd, torch.from_numpy(g['x']), outs
 
 
 SAMPLE_CASES = ['tiny', 'tiny_k6', 'tiny_noar', 'metric']

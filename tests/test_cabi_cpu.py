@@ -73,6 +73,7 @@ def test_flags_registered_like_the_reference():
 
 def test_forge_load_entry_point(tmp_path):
     """fet.load(model_config_path, cfg) -> load(cfg): the call train.py:152 makes."""
+    import genesis_amd.genesisv2_config  # noqa: F401  (installs the forge stand-in, whatever ran before this test)
     from forge import experiment_tools as fet
     from genesis_amd.compat.attrdict import AttrDict
     path = osp.join(REPO, 'genesis_amd', 'genesisv2_config.py')

@@ -41,6 +41,14 @@ def _local_grads(x, rp, eps):
     return bucket
 
 
+def _kl_terms(x, rp, eps):
+    """mean_b sum_k |kl_l_k|: the magnitude of the terms the batch-mean KL sums."""
+    with torch.no_grad():
+        _, losses, _, _, _ = O.v2_forward(T.formula_state_dict(O.template_state_dict(CFG)), x, CFG, rp, eps,
+                                          reference_form=False)
+    return float(torch.stack(losses['kl_l_k'], 1).abs().sum(1).mean())
+
+
 def _worker(rank, world, port, out_dir):
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
@@ -72,8 +80,11 @@ def test_two_rank_bucket_equals_full_batch(tmp_path):
     n32 = full.n32
     rel = float((got[:n32] - ref[:n32]).norm() / ref[:n32].norm())
     assert rel < 1e-4, rel
-    # global err, kl right behind the parameters' gradients (the fp64 gradient's (hi, mid, lo) triple follows them)
-    np.testing.assert_allclose(got[n32:n32 + 2].numpy(), ref[n32:n32 + 2].numpy(), rtol=1e-5)
+    # global err, kl right behind the parameters' gradients (the fp64 gradient's (hi, mid, lo) triple follows them).  The
+    # batch-mean KL is a small sum of larger terms of both signs (|kl| ~ 0.09 here from sum_k |kl_l_k| ~ 3 per image): its fp32
+    # rounding, which differs with the host CPU's vector kernels, is bounded relative to those terms, not to their sum
+    np.testing.assert_allclose(got[n32].item(), ref[n32].item(), rtol=1e-5)
+    np.testing.assert_allclose(got[n32 + 1].item(), ref[n32 + 1].item(), rtol=1e-5, atol=1e-5 * _kl_terms(x, rp, eps))
     np.testing.assert_allclose(r0['g64'].numpy(), full.flat_g64.detach().numpy(), rtol=1e-4, atol=1e-7)
 
 

@@ -1,5 +1,5 @@
 """Pins oracle/monet_oracle.py (BASELINE config 4) against golden vectors captured from the real reference MONet,
-and live against the import when /root/reference is present."""
+and against the reference's own model: the live import when the reference tree is present, its recording otherwise."""
 import json
 import os.path as osp
 
@@ -10,6 +10,7 @@ import torch
 from genesis_amd import testing as T
 from oracle import monet_oracle as M
 from oracle import ref_import as R
+from tests.common import load_live_recording
 
 GOLDEN = osp.join(osp.dirname(osp.abspath(__file__)), 'golden')
 CASES = ['tiny', 'tiny_k4', 'cfg4', 'tiny_scope']
@@ -96,22 +97,38 @@ def test_forward_and_grads(case):
         assert float((torch.stack(stats[key], 4).exp().sum(4) - 1).abs().max()) < 1e-3
 
 
-@pytest.mark.skipif(not R.reference_available(), reason='reference tree not present')
-def test_live_against_reference_import():
-    mods = R.import_reference()
-    cfg = M.make_cfg(K_steps=4, img_size=32)
+LIVE_CFG = dict(K_steps=4, img_size=32)
+
+
+def live_reference_run(mods):
+    """The reference's own MONet (initialised under seed 2) -- its state_dict is returned as it initialised it --, run on the
+    closed-form weights of the golden fixtures (genesis_amd.testing.formula_state_dict of that state_dict) on x ~ U[0, 1),
+    forward under noise seed 5: (state_dict, x, outputs).  Recorded for machines without the reference by
+    tests/golden/make_golden_live.py."""
     torch.manual_seed(2)
-    ref = mods['monet_config'].load(R.reference_cfg(**cfg))
-    sd = ref.state_dict()
+    ref = mods['monet_config'].load(R.reference_cfg(**M.make_cfg(**LIVE_CFG)))
+    sd = {k: v.clone() for k, v in ref.state_dict().items()}
+    ref.load_state_dict(T.formula_state_dict(sd))
+    x = torch.rand(2, 3, 32, 32)
+    torch.manual_seed(5)
+    r = ref(x)
+    return sd, x, {'recon': r[0], 'err': r[1]['err'], 'kl_m': r[1]['kl_m']}
+
+
+def test_live_against_reference_import():
+    """The oracle against the reference's own MONet: imported live when the reference tree is present, else that same run as
+    recorded from the import (tests/golden/live_monet.npz)."""
+    if R.reference_available():
+        sd, x, r = live_reference_run(R.import_reference())
+    else:
+        sd, x, r = load_live_recording('monet')
+    cfg = M.make_cfg(**LIVE_CFG)
     want = M.param_shapes(cfg)
     assert list(sd.keys()) == list(want.keys())
     for k, (shape, _) in want.items():
         assert tuple(sd[k].shape) == tuple(shape), k
-    x = torch.rand(2, 3, 32, 32)
     torch.manual_seed(5)
-    r = ref(x)
-    torch.manual_seed(5)
-    o = M.monet_forward({k: v for k, v in sd.items()}, x, cfg)
-    assert torch.allclose(r[0], o[0], atol=1e-6)
-    assert torch.allclose(r[1]['err'], o[1]['err'], rtol=1e-6)
-    assert torch.allclose(r[1]['kl_m'], o[1]['kl_m'], rtol=1e-5, atol=1e-5)
+    o = M.monet_forward(T.formula_state_dict(sd), x, cfg)
+    assert torch.allclose(r['recon'], o[0], atol=1e-6)
+    assert torch.allclose(r['err'], o[1]['err'], rtol=1e-6)
+    assert torch.allclose(r['kl_m'], o[1]['kl_m'], rtol=1e-5, atol=1e-5)

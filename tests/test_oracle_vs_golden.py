@@ -1,12 +1,13 @@
 """Pins the oracle (oracle/v2_oracle.py) against golden vectors captured from the real
-reference, and -- when /root/reference is present -- against the live import."""
+reference, and against the reference's own model: the live import when the reference tree is present, its recording otherwise."""
 import numpy as np
 import pytest
 import torch
 
+from genesis_amd import testing as T
 from oracle import v2_oracle as O
 from oracle import ref_import as R
-from tests.common import ALL_CASES, DYN_CASES, SAMPLE_CASES, Golden, SampleGolden
+from tests.common import ALL_CASES, DYN_CASES, SAMPLE_CASES, Golden, SampleGolden, load_live_recording
 
 
 def _params(gold, requires_grad=False):
@@ -73,29 +74,50 @@ def test_sample_vs_golden(case):
                    mx_k=[x * m.exp() for x, m in zip(x_k, log_m_k)])
 
 
-@pytest.mark.skipif(not R.reference_available(), reason='reference tree not present')
-def test_live_against_reference_import():
-    mods = R.import_reference()
-    cfgd = O.make_cfg(K_steps=5, img_size=32, feat_dim=16)
-    cfg = R.reference_cfg(**cfgd)
+LIVE_CFG = dict(K_steps=5, img_size=32, feat_dim=16)
+
+
+def live_weights(sd):
+    """The weights both sides run on: closed-form (genesis_amd.testing.formula_state_dict, the golden fixtures' weights, a
+    function of the names, shapes and dtypes of `sd`), colour-head gate 0.4."""
+    w = T.formula_state_dict(sd)
+    w['att_process.colour_head.gate.gate'] = torch.tensor(0.4, dtype=sd['att_process.colour_head.gate.gate'].dtype)
+    return w
+
+
+def live_reference_run(mods):
+    """The reference's own model (initialised under seed 3) -- its state_dict is returned as it initialised it --, run on
+    live_weights on x ~ U[0, 1), forward under noise seed 5: (state_dict, x, outputs).  Recorded for machines without the
+    reference by tests/golden/make_golden_live.py."""
     torch.manual_seed(3)
-    model = mods['genesisv2_config'].load(cfg)
-    sd = model.state_dict()
+    model = mods['genesisv2_config'].load(R.reference_cfg(**O.make_cfg(**LIVE_CFG)))
+    sd = {k: v.clone() for k, v in model.state_dict().items()}
+    model.load_state_dict(live_weights(sd))
+    x = torch.rand(3, 3, 32, 32)
+    torch.manual_seed(5)
+    r_recon, r_losses, r_stats, _, r_comp = model(x)
+    return sd, x, {'recon': r_recon, 'err': r_losses['err'], 'kl_l_k': torch.stack(r_losses['kl_l_k']),
+                   'z_k': torch.stack(r_comp['z_k'])}
+
+
+def test_live_against_reference_import():
+    """The oracle against the reference's own model and forward: imported live when the reference tree is present, else
+    that same run as recorded from the import (tests/golden/live_v2.npz)."""
+    if R.reference_available():
+        sd, x, r = live_reference_run(R.import_reference())
+    else:
+        sd, x, r = load_live_recording('v2')
+    cfgd = O.make_cfg(**LIVE_CFG)
     assert list(sd.keys()) == list(O.param_shapes(cfgd).keys())
     for k, (shape, dt) in O.param_shapes(cfgd).items():
         assert tuple(sd[k].shape) == tuple(shape) and sd[k].dtype == dt, k
     assert torch.equal(sd['att_process.log_sigma'], O.default_log_sigma(cfgd).double())
-    with torch.no_grad():
-        sd['att_process.colour_head.gate.gate'].fill_(0.4)
-    model.load_state_dict(sd)
-    x = torch.rand(3, 3, 32, 32)
-    torch.manual_seed(5)
-    r_recon, r_losses, r_stats, _, r_comp = model(x)
     torch.manual_seed(5)  # oracle draws its own noise in the same order
-    recon, losses, stats, _, comp = O.v2_forward({k: v for k, v in sd.items()}, x, cfgd)
-    assert torch.allclose(recon, r_recon, rtol=1e-5, atol=1e-6)
-    assert torch.allclose(losses['err'], r_losses['err'], rtol=1e-6)
-    for a, b in zip(losses['kl_l_k'], r_losses['kl_l_k']):
+    recon, losses, stats, _, comp = O.v2_forward(live_weights(sd), x, cfgd)
+    assert torch.allclose(recon, r['recon'], rtol=1e-5, atol=1e-6)
+    assert torch.allclose(losses['err'], r['err'], rtol=1e-6)
+    for a, b in zip(losses['kl_l_k'], r['kl_l_k']):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-5)
-    for a, b in zip(comp['z_k'], r_comp['z_k']):
+    assert len(comp['z_k']) == len(r['z_k'])
+    for a, b in zip(comp['z_k'], r['z_k']):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-6)
