@@ -284,7 +284,9 @@ class UNetEncoderFn(torch.autograd.Function):
                                                         (nxt, 0, 0), amax_in=am_cur)
                 mlp_in = nxt
             am_in.append(am_cur)
-            am_cur = am_cat[j][1] = hip.take_amax()          # (the skip slice and the resampled copy hold the same values)
+            am_cat[j][1] = hip.take_amax()          # (the skip slice holds the layer's values)
+            # the down-sampled copy ([::2, ::2]) holds a subset of them: its largest magnitude may be smaller -- a pass of its own
+            am_cur = hip.amax_of(nxt) if i < nb - 1 and am_cat[j][1] is not None else am_cat[j][1]
             saved_down.append((cur, y, mean, rstd))
             cur = nxt
         # bottleneck MLP: three Linear+ReLU on the dense MFMA kernel (modules/unet.py:58-62,83)

@@ -121,6 +121,7 @@ def _tap_begin(device, hw, numel):
 
 def _tap_end(tap):
     if tap is None:
+        _LAST.amax = None          # (a launch that did not tap: take_amax() must not hand out an earlier launch's handle)
         return
     ptr, a, off = tap
     n = _lib.query('gx_amax_tap_result')
@@ -136,6 +137,21 @@ def amax_values(h, device=None):
     off = (h.ptr - a[1]) // 4
     assert 0 <= off and off + h.n <= _ARENA_FLOATS, 'not an arena handle'
     return a[0][off:off + h.n]
+
+
+def amax_fill(value, device=None):
+    """Every float of the device's partial-maxima arena set to `value` (a NaN sentinel shows a slot no producer wrote) -- tests."""
+    _, a, _ = _amax_scratch(device if device is not None else torch.device('cuda', torch.cuda.current_device()), 0)
+    a[0].fill_(float(value))
+
+
+def amax_handle(values, device=None):
+    """An Amax handle whose partial maxima are `values` (copied into the arena) -- tests."""
+    v = torch.as_tensor(values, dtype=F32).flatten()
+    dev = device if device is not None else torch.device('cuda', torch.cuda.current_device())
+    ptr, a, off = _amax_scratch(dev, v.numel())
+    a[0][off:off + v.numel()].copy_(v.to(a[0].device))
+    return Amax(ptr, v.numel())
 
 
 def amax_of(t):
@@ -726,8 +742,7 @@ def conv1x1_bwd_act(x, dy, w, bias, act, out=None, dbx_out=None, want_dbx=True, 
     t = _tap_begin(dev, 1 << 30, dxa.numel()) if tap else None      # (tap: dxa's partial maxima, take_amax() afterwards)
     _lib.call('gx_conv1x1_bwd_act', _p(x), _p(dy), _p(w), _p(bias), N, Cin, Cout, H, W, ACTS[act], _p(dxa), _p(dw), _p(db),
               _p(dbx), _p(ws), nb, _stream())
-    if tap:
-        _tap_end(t)
+    _tap_end(t)
     return dxa, (dw.view(w.shape) if o[0] is None else dw), db, dbx
 
 
@@ -753,8 +768,7 @@ def bcast_conv3x3_fwd(z, w, bias, rowc, colc, act, tap=False):
     t = _tap_begin(z.device, 1 << 30, out.numel()) if tap else None      # (tap: out's partial maxima, take_amax() afterwards)
     _lib.call('gx_bcast_conv3x3_fwd', _p(z), _p(w), _p(bias), _p(rowc), _p(colc), ACTS[act], _p(out), N, L, Co, d,
               _stream())
-    if tap:
-        _tap_end(t)
+    _tap_end(t)
     return out
 
 
@@ -843,8 +857,7 @@ def conv3x3_bias_act_fwd(x, w, bias, act, amax_in=None, tap=False):
     with _input_amax(amax_in):
         _lib.call('gx_conv3x3_bias_act_fwd', _p(x), _p(w), _p(bias), ACTS[act], _p(y), N, Cin, Cout, H, W, _p(ws), nb,
                   _stream())
-    if tap:
-        _tap_end(t)
+    _tap_end(t)
     return y
 
 
@@ -883,8 +896,7 @@ def conv3x3_dgrad_act(dy, w, xout, act, dbias_out=None, want_dbias=True, amax_in
     with _input_amax(amax_in):
         _lib.call('gx_conv3x3_dgrad_act', _p(dy), _p(w), _p(xout), ACTS[act], _p(dxa), _p(dbias), N, Cin, Cout, H, W, _p(ws), nb,
                   _stream())
-    if tap:
-        _tap_end(t)
+    _tap_end(t)
     return dxa, dbias
 
 
