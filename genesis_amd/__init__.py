@@ -1,0 +1,1 @@
+from .precision import get_matmul_precision, set_matmul_precision  # noqa: F401

@@ -29,6 +29,7 @@ from torch.nn.parallel import DistributedDataParallel as _DDP
 
 from . import _lib
 from . import hip_ops as _hip
+from . import precision as _precision
 
 ENABLED = os.environ.get('GENESIS_AUTOSTEP', '1') != '0'
 
@@ -123,10 +124,10 @@ def arm(model, x=None):
     st.ctx = _lib.current_ctx()
     book = _book(model)
     cache = book['cache']
-    key = _param_key(model)
+    key = (_param_key(model), _precision.level())
     if cache is not None and cache[2] != key:
-        # the parameters moved (a TrainStep re-homed them into its flat bucket, .to(), load of another state): the recorded
-        # (weight pointer, layout) pairs are stale -- start over
+        # the parameters moved (a TrainStep re-homed them into its flat bucket, .to(), load of another state) or the matmul
+        # precision changed (the packings are laid out per level): the recorded (weight pointer, layout) pairs are stale -- start over
         _lib.call('gx_weight_cache_destroy', cache[0])
         cache[0], cache[1], cache[2] = int(_lib.query('gx_weight_cache_create')), False, key
     if cache is None:
@@ -305,7 +306,8 @@ def graph_stats(model):
 
 
 def _graph_key(model, x):
-    return (tuple(x.shape), x.dtype, x.device, _param_key(model), bool(getattr(model, 'klm_loss', False)))
+    # (the matmul precision level: a graph captured at another level holds that level's kernels and packings)
+    return (tuple(x.shape), x.dtype, x.device, _param_key(model), bool(getattr(model, 'klm_loss', False)), _precision.level())
 
 
 def _drop_graph(g):
@@ -320,11 +322,13 @@ class _ReplayFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dummy, g):
         ctx.g = g
+        ctx.level = _precision.level()
         ctx.set_materialize_grads(False)
         return tuple(t.detach() for t in g.roots)
 
     @staticmethod
     def backward(ctx, *grads):
+        _precision.check_backward(ctx.level)
         _graph_backward(ctx.g, grads)
         return None, None
 

@@ -1,6 +1,8 @@
 // Error plumbing + version for libgenesis_hip.so.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <strings.h>
 
 #include <vector>
 
@@ -115,6 +117,40 @@ int gx_profile_collect(double* total_ms, double* launches, double* flops, double
 
 const char* gx_last_error(void) { return g_err; }
 int gx_version(void) { return 1; }
+
+// ---- one switch for the three 16-bit-pipe conv families (include/genesis_hip.h: gx_matmul_precision) ----------------
+static int matmul_level_of(int kq, int wgq, int wino) {
+    for (int lv = 0; lv < 3; ++lv) {
+        const int m = gx_matmul_level_mode(lv);
+        if (kq == m && wgq == m && wino == m) return lv;
+    }
+    return GX_MATMUL_MIXED;
+}
+int gx_matmul_precision_get(void) { return matmul_level_of(gx_kq_mode_now(), gx_wgq_mode_now(), gx_wino_mode_now()); }
+int gx_matmul_precision(int level) {
+    GX_CHECK_ARG(level >= -1 && level <= 2, "gx_matmul_precision: level must be 0 (highest: fp32 pipe), 1 (high: today's defaults), "
+                                             "2 (medium: one bf16 piece per operand) or -1 (the environment's defaults)");
+    const int prev = gx_matmul_precision_get();
+    const int m = level < 0 ? -1 : gx_matmul_level_mode(level);
+    gx_kq_precision(m);
+    gx_wgq_precision(m);
+    gx_wino_precision(m);
+    return prev;
+}
+}
+
+// GENESIS_MATMUL_PRECISION=highest|high|medium: -1 when unset; an unknown value is reported once and ignored
+int gx_env_matmul_level(void) {
+    static const int lv = [] {
+        const char* e = getenv("GENESIS_MATMUL_PRECISION");
+        if (!e || !e[0]) return -1;
+        if (!strcasecmp(e, "highest")) return 0;
+        if (!strcasecmp(e, "high")) return 1;
+        if (!strcasecmp(e, "medium")) return 2;
+        fprintf(stderr, "libgenesis_hip: GENESIS_MATMUL_PRECISION=%s is not one of highest, high, medium -- ignored\n", e);
+        return -1;
+    }();
+    return lv;
 }
 
 // ---- deferred parameter-gradient reductions -------------------------------------------------------------

@@ -142,8 +142,9 @@ __host__ __device__ __forceinline__ size_t gx_wino_u_slot(int m, int k, int p, i
 // reduction channels.  32-bit word (two channels k even, k + 1) of piece `piece` of position p:
 // [m tile 64][chunk k >> 4][position 16][piece 3][m half (m >> 5) & 1][lane = 32 ((k >> 3) & 1) + (m & 31)][(k & 7) >> 1]
 // -- a wave's A operand of (position, piece, m half) is 1 KB, lane-linear: one 16-byte load per lane.
-__host__ __device__ __forceinline__ size_t gx_wino_h_word(int m, int k, int p, int piece, int Kpad16) {
-    return ((((((size_t)(m >> 6) * (Kpad16 >> 4) + (k >> 4)) * 16 + p) * 3 + piece) * 2 + ((m >> 5) & 1)) * 256) +
+// (NP = 1: the one-piece form, gx_wino_precision(3) -- one bf16 piece per value, positions 2 KB apart instead of 6 KB)
+__host__ __device__ __forceinline__ size_t gx_wino_h_word(int m, int k, int p, int piece, int Kpad16, int NP = 3) {
+    return ((((((size_t)(m >> 6) * (Kpad16 >> 4) + (k >> 4)) * 16 + p) * NP + piece) * 2 + ((m >> 5) & 1)) * 256) +
            (size_t)((((k >> 3) & 1) * 32 + (m & 31)) * 4 + ((k & 7) >> 1));
 }
 __host__ __device__ __forceinline__ size_t gx_wino_h_bytes(int Kpad16, int Mpad) {
@@ -152,6 +153,7 @@ __host__ __device__ __forceinline__ size_t gx_wino_h_bytes(int Kpad16, int Mpad)
 bool gx_wino_h_on();     // Winograd layers on the bf16 pipe (default; gx_wino_precision(0) / GENESIS_WINO_BF16X6=0: fp32 pipe)
 bool gx_conv_input_hint(const float** p0, int* n0, const float** p1, int* n1);      // the armed gx_conv_input_amax hint (gx_wino.hip), not cleared
 bool gx_wino_f16_pending(void);   // ... and the NEXT launch of this thread on two fp16 pieces per operand (gx_conv_input_amax armed): pack kinds 45 / 46
+bool gx_wino_b1_on(void);         // ... on ONE bf16 piece per operand (gx_wino_precision(3)): pack kinds 65 / 66
 // conv with an already packed U (16 * Kpad * Mpad floats; bf16 pipe: gx_wino_h_bytes): out[N,M,H,W] from in[N,K,H,W]
 bool gx_wino_eligible(int N, int K, int M, int H, int W);
 int gx_wino_launch(const float* in, const float* U, float* out, int N, int K, int M, int H, int W, hipStream_t s);
@@ -188,6 +190,16 @@ size_t gx_kq_deconv_h_pack_bytes(int K, int M, int nt);
 // 40 / 41 / 42 / 43 / 44 / 47 / 48 = 20 / 21 / 22 / 23 / 24 / 27 / 28 as two fp16 pieces of w * 2^e (two piece slots per tap); the weight tensor's amax lives in the last
 // 64 bytes of the packing's slack (written by the amax launch that precedes the pack, read by the pack and by the conv kernels).
 bool gx_kq_f16_on();
+// ... or from ONE bf16 piece per operand (gx_kq_precision(3)): packs 60 .. 68 = 20 .. 28 as one bf16 piece (round to nearest even)
+bool gx_kq_b1_on();
+__host__ __device__ __forceinline__ bool gx_pack_f16(int pack) { return pack >= 40 && pack < 60; }
+// GENESIS_MATMUL_PRECISION (gx_api.cpp): -1 unset, else the level 0 highest / 1 high / 2 medium -- read by every family's default
+// ahead of its own variables; gx_matmul_level_mode: the family mode of a level (0 -> 0, 1 -> 2, 2 -> 3)
+int gx_env_matmul_level(void);
+inline int gx_matmul_level_mode(int level) { return level == 0 ? 0 : (level == 1 ? 2 : 3); }
+int gx_kq_mode_now(void);         // the resolved mode of each family (gx_matmul_precision)
+int gx_wgq_mode_now(void);
+int gx_wino_mode_now(void);
 __host__ __device__ __forceinline__ size_t gx_kq_h_amax_off(int K, int M, int nt) {      // byte offset of that float
     return (size_t)((M + 63) / 64) * (K / 16) * nt * 6144 + 16384 - 64;
 }

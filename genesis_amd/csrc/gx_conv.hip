@@ -562,16 +562,23 @@ __device__ __forceinline__ size_t pack_dest(int pack, int idx, int m, int k, int
 // packs 25 / 26 (= 5 / 6: the Winograd operands for gx_wino.hip's bf16-pipe kernel), 20 / 21 (= 0 / 1, gx_kq.hip's Q_C3H) and 22 / 23 / 24 (= 2 / 3 / 4 for the bf16 matrix pipe, gx_kq.hip's QCfgDTH / Q_DGH): every weight as three bf16 pieces, two
 // channels per 32-bit word -- the thread of an even k writes the three words of (k, k + 1), the odd one nothing
 // packs 42 / 43 / 44: 22 / 23 / 24 as TWO fp16 pieces of w * 2^f16_exp (gx_kq.hip's fp16 x 3 form; f16_exp from the tensor's amax)
+// packs 60 .. 68: 20 .. 28 as ONE bf16 piece, w rounded to nearest even (the one-piece form, gx_matmul_precision(2))
 __device__ __forceinline__ void pack_h_store(const float* __restrict__ w, float* __restrict__ wp, int pack, int Co, int Ci,
                                              int m, int k, int t, int NT, int Kpad, int f16_exp = 0) {
     if (k & 1) return;
-    const bool f16 = pack >= 40;
+    const bool f16 = gx_pack_f16(pack), b1 = pack >= 60;
     if (f16) pack -= 20;
+    if (b1) pack -= 40;
     unsigned wd[3];
     float v[2] = {pack_weight_value(w, pack - 20, Co, Ci, m, k, t), pack_weight_value(w, pack - 20, Co, Ci, m, k + 1, t)};
     unsigned short pc[2][3];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
+        if (b1) {
+            pc[e][0] = __builtin_bit_cast(unsigned short, (__bf16)v[e]);
+            pc[e][1] = pc[e][2] = 0;
+            continue;
+        }
         if (f16) {
             const float ws = ldexpf(v[e], f16_exp);
             const _Float16 h = (_Float16)ws;
@@ -588,13 +595,13 @@ __device__ __forceinline__ void pack_h_store(const float* __restrict__ w, float*
         pc[e][1] = __builtin_bit_cast(unsigned short, mm);
         pc[e][2] = __builtin_bit_cast(unsigned short, l);
     }
-    const int np = f16 ? 2 : 3;
+    const int np = b1 ? 1 : (f16 ? 2 : 3);
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         if (q >= np) break;
         wd[q] = (unsigned)pc[0][q] | ((unsigned)pc[1][q] << 16);
         const size_t dst = pack <= 21 ? gx_kq_h32_word(m, k, t, q, NT, Kpad, np)       // 20 / 21: conv3x3, 32-channel tiles
-                           : ((pack == 25 || pack == 26) ? gx_wino_h_word(m, k, t, q, Kpad)        // 25 / 26: Winograd operands (= 5 / 6), t = position; 27 / 28: 5 x 5 stride 1 (= 7 / 8)
+                           : ((pack == 25 || pack == 26) ? gx_wino_h_word(m, k, t, q, Kpad, b1 ? 1 : 3)   // 25 / 26: Winograd operands (= 5 / 6), t = position; 27 / 28: 5 x 5 stride 1 (= 7 / 8)
                                          : gx_kq_h_word(m, k, pack == 24 ? gx_kq_dg_tap_slot(t) : t, q, NT, Kpad, np));
         wp[dst] = __builtin_bit_cast(float, wd[q]);
     }
@@ -603,7 +610,7 @@ __device__ __forceinline__ void pack_h_store(const float* __restrict__ w, float*
 __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ wp, int pack,
                                     int Co, int Ci, int NT, int Kpad, int Mpad) {
     const int total = NT * Kpad * Mpad;
-    const int f16_exp = pack >= 40 ? gx_f16_scale_exp(((pack == 45 || pack == 46) ? 2.25f : 1.f) * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp) + gx_kq_h_amax_off(Kpad, Mpad, NT))) : 0;
+    const int f16_exp = gx_pack_f16(pack) ? gx_f16_scale_exp(((pack == 45 || pack == 46) ? 2.25f : 1.f) * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp) + gx_kq_h_amax_off(Kpad, Mpad, NT))) : 0;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int m = idx % Mpad;
         const int k = (idx / Mpad) % Kpad;
@@ -1571,7 +1578,7 @@ std::mutex g_cache_mutex;
 __global__ void __launch_bounds__(1024)
 pack_amax_batch_kernel(const PackEntry* __restrict__ entries) {
     const PackEntry e = entries[blockIdx.x];
-    if (e.pack < 40) return;
+    if (!gx_pack_f16(e.pack)) return;
     const float r = gx_wg1024_amax(e.w, e.Co * e.Ci * ((e.pack <= 41 || e.pack == 45 || e.pack == 46) ? 9 : 25));
     if (threadIdx.x == 0) *reinterpret_cast<float*>(reinterpret_cast<char*>(e.wp) + gx_kq_h_amax_off(e.Kpad, e.Mpad, e.NT)) = r;
 }
@@ -1581,7 +1588,7 @@ __global__ void pack_weights_batch_kernel(const PackEntry* __restrict__ entries,
     const int total = e.NT * e.Kpad * e.Mpad;
     const int begin = (blockIdx.x - e.chunk0) * kPackChunk, end = begin + kPackChunk < total ? begin + kPackChunk : total;
     // (45 / 46: the Winograd operands U = G g G^T, |U| <= 2.25 max |g|)
-    const int f16_exp = e.pack >= 40 ? gx_f16_scale_exp(((e.pack == 45 || e.pack == 46) ? 2.25f : 1.f) * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(e.wp) + gx_kq_h_amax_off(e.Kpad, e.Mpad, e.NT))) : 0;
+    const int f16_exp = gx_pack_f16(e.pack) ? gx_f16_scale_exp(((e.pack == 45 || e.pack == 46) ? 2.25f : 1.f) * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(e.wp) + gx_kq_h_amax_off(e.Kpad, e.Mpad, e.NT))) : 0;
     for (int idx = begin + threadIdx.x; idx < end; idx += blockDim.x) {
         const int m = idx % e.Mpad;
         const int k = (idx / e.Mpad) % e.Kpad;
@@ -1615,7 +1622,7 @@ int launch_pack(const float* w, float* wp, int pack, int Co, int Ci, int NT, int
     }
     const int total = NT * Kpad * Mpad;
     const int blocks = gx_ceil_div(total, 256) > 1024 ? 1024 : gx_ceil_div(total, 256);
-    if (pack >= 40) {
+    if (gx_pack_f16(pack)) {
         const int rc = gx_kq_weight_amax_launch(w, Co * Ci * ((pack <= 41 || pack == 45 || pack == 46) ? 9 : 25), reinterpret_cast<float*>(reinterpret_cast<char*>(wp) + gx_kq_h_amax_off(Kpad, Mpad, NT)), s);
         if (rc) return rc;
     }
@@ -2254,7 +2261,7 @@ int gx_weight_cache_refresh(int id, gx_stream_t stream) {
     if (c.entries.empty()) { g_cache_active = -1; return GX_OK; }
     hipStream_t s = (hipStream_t)stream;
     bool any_f16 = false;
-    for (const PackEntry& e : c.entries) any_f16 = any_f16 || e.pack >= 40;
+    for (const PackEntry& e : c.entries) any_f16 = any_f16 || gx_pack_f16(e.pack);
     if (any_f16) {
         GxProf pf(KID_SMALL_REDUCE, s, 0.0, 0.0);
         hipLaunchKernelGGL(pack_amax_batch_kernel, dim3((unsigned)c.entries.size()), dim3(1024), 0, s, (const PackEntry*)c.dev);
@@ -2369,7 +2376,8 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
     static const char* c3h_first = getenv("GENESIS_KQ_C3H_FIRST");
     if ((!wino_ok || !(c3h_first && c3h_first[0] == '0')) && gx_kq_c3h_eligible(N, Cin, Cout, H, W)) {
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 40: two fp16 pieces of w * 2^e (gx_kq_precision(2))
-        rc = launch_pack(w, wp, 20 + f16, Cout, Cin, 9, gx_round_up(Cin, 16), Mpad, s, &wpu);
+        const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 60: one bf16 piece (gx_kq_precision(3))
+        rc = launch_pack(w, wp, 20 + f16 + b1, Cout, Cin, 9, gx_round_up(Cin, 16), Mpad, s, &wpu);
         if (rc) return rc;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_conv3x3_ws_bytes(N, Cin, Cout, H, W)) - gx_kq_amax_ws_floats() : nullptr;
         if (f16) { int unused_n; (void)gx_amax_link_take(nullptr, 0, &unused_n); }       // (a pending amax link is not for this call)
@@ -2389,7 +2397,7 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
     }
     if (wino_ok) {   // Winograd F(2x2,3x3): 2.25x fewer MFMA passes
         // (25: three bf16 pieces; 45: two fp16 pieces -- the input's maxima were handed in, gx_conv_input_amax)
-        rc = gx_wino_h_on() ? launch_pack(w, wp, gx_wino_f16_pending() ? 45 : 25, Cout, Cin, 16, gx_round_up(Cin, 16), Mpad, s, &wpu)
+        rc = gx_wino_h_on() ? launch_pack(w, wp, gx_wino_f16_pending() ? 45 : (gx_wino_b1_on() ? 65 : 25), Cout, Cin, 16, gx_round_up(Cin, 16), Mpad, s, &wpu)
                             : launch_pack(w, wp, 5, Cout, Cin, 16, Kpad, Mpad, s, &wpu);
         if (rc) return rc;
         rc = gx_wino_launch(x, wpu, y, N, Cin, Cout, H, W, s);
@@ -2448,7 +2456,8 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
     static const char* c3h_first = getenv("GENESIS_KQ_C3H_FIRST");
     if ((!wino_ok || !(c3h_first && c3h_first[0] == '0')) && gx_kq_c3h_eligible(N, Cout, Cin, H, W)) {
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 41
-        rc = launch_pack(w, wp, 21 + f16, Cout, Cin, 9, gx_round_up(Cout, 16), Mpad, s, &wpu);
+        const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 61
+        rc = launch_pack(w, wp, 21 + f16 + b1, Cout, Cin, 9, gx_round_up(Cout, 16), Mpad, s, &wpu);
         if (rc) return rc;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_conv3x3_ws_bytes(N, Cin, Cout, H, W)) - gx_kq_amax_ws_floats() : nullptr;
         if (f16) { int unused_n; (void)gx_amax_link_take(nullptr, 0, &unused_n); }       // (a pending amax link is not for this call)
@@ -2461,7 +2470,7 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
         return gx_kq_c3_launch(dy, wpu, nullptr, 0, dx, N, Cout, Cin, H, W, s);
     }
     if (wino_ok) {
-        rc = gx_wino_h_on() ? launch_pack(w, wp, gx_wino_f16_pending() ? 46 : 26, Cout, Cin, 16, gx_round_up(Cout, 16), Mpad, s, &wpu)
+        rc = gx_wino_h_on() ? launch_pack(w, wp, gx_wino_f16_pending() ? 46 : (gx_wino_b1_on() ? 66 : 26), Cout, Cin, 16, gx_round_up(Cout, 16), Mpad, s, &wpu)
                             : launch_pack(w, wp, 6, Cout, Cin, 16, Kpad, Mpad, s, &wpu);
         if (rc) return rc;
         return gx_wino_launch(dy, wpu, dx, N, Cout, Cin, H, W, s);
@@ -2501,7 +2510,8 @@ int gx_conv3x3_dgrad_act(const float* dy, const float* w, const float* xout, int
     hipStream_t s = (hipStream_t)stream;
     const float* wpu;
     const int f16 = gx_kq_f16_on() ? 20 : 0;           // pack 41
-    rc = launch_pack(w, (float*)ws, 21 + f16, Cout, Cin, 9, gx_round_up(Cout, 16), gx_round_up(Cin, 64), s, &wpu);
+    const int b1 = gx_kq_b1_on() ? 40 : 0;             // pack 61
+    rc = launch_pack(w, (float*)ws, 21 + f16 + b1, Cout, Cin, 9, gx_round_up(Cout, 16), gx_round_up(Cin, 64), s, &wpu);
     if (rc) return rc;
     float* amax_ws = f16 ? (float*)((char*)ws + gx_conv3x3_ws_bytes(N, Cin, Cout, H, W)) - gx_kq_amax_ws_floats() : nullptr;
     if (f16) { int unused_n; (void)gx_amax_link_take(nullptr, 0, &unused_n); }       // (a pending amax link is not for this call)
@@ -2701,8 +2711,9 @@ int gx_conv5x5s1(const float* in, const float* w, float* out, int N, int K, int 
     const float* wpu;
     if (gx_kq_c5h_eligible(N, K, M, H, W)) {       // chip-filling layers: on the bf16 matrix pipe (gx_kq.hip Q_C5H)
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // packs 47 / 48
-        rc = flip ? launch_pack(w, wp, 28 + f16, K, M, 25, gx_round_up(K, 16), Mpad, s, &wpu)
-                  : launch_pack(w, wp, 27 + f16, M, K, 25, gx_round_up(K, 16), Mpad, s, &wpu);
+        const int b1 = gx_kq_b1_on() ? 40 : 0;         // packs 67 / 68
+        rc = flip ? launch_pack(w, wp, 28 + f16 + b1, K, M, 25, gx_round_up(K, 16), Mpad, s, &wpu)
+                  : launch_pack(w, wp, 27 + f16 + b1, M, K, 25, gx_round_up(K, 16), Mpad, s, &wpu);
         if (rc) return rc;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_conv5x5s1_ws_bytes(N, K, M, H, W)) - gx_kq_amax_ws_floats() : nullptr;
         int xn = 0;
@@ -2853,9 +2864,10 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
     if (gx_kq_deconv_h_eligible(N, Cin, Cout, Hin, Win)) {     // ... on the bf16 matrix pipe (fp32 products from bf16 pieces)
         float* wh1 = wp0 + gx_kq_deconv_h_pack_bytes(Cin, Cout, 15) / 4;
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // packs 42 / 43: two fp16 pieces of w * 2^e (gx_kq_precision(2))
-        rc = launch_pack(w, wp0, 22 + f16, Cout, Cin, 15, Cin, Mpad, s, &wpu0);
+        const int b1 = gx_kq_b1_on() ? 40 : 0;         // packs 62 / 63: one bf16 piece (gx_kq_precision(3))
+        rc = launch_pack(w, wp0, 22 + f16 + b1, Cout, Cin, 15, Cin, Mpad, s, &wpu0);
         if (rc) return rc;
-        rc = launch_pack(w, wh1, 23 + f16, Cout, Cin, 10, Cin, Mpad, s, &wpu1);
+        rc = launch_pack(w, wh1, 23 + f16 + b1, Cout, Cin, 10, Cin, Mpad, s, &wpu1);
         if (rc) return rc;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_deconv5x5s2_ws_bytes(N, Cin, Cout, Hin, Win)) - gx_kq_amax_ws_floats() : nullptr;
         int xn = 0;
@@ -2950,7 +2962,8 @@ int gx_deconv5x5s2_dgrad(const float* dy, const float* w, float* dx, int N, int 
     const float* wpu;
     if (gx_kq_deconv_dgrad_h_eligible(N, Cout, Cin_out, Hin, Win)) {     // on the bf16 matrix pipe
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 44 (gx_kq_precision(2))
-        rc = launch_pack(w, wp, 24 + f16, Cout, Cin, 25, Cout, Mpad, s, &wpu);
+        const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 64 (gx_kq_precision(3))
+        rc = launch_pack(w, wp, 24 + f16 + b1, Cout, Cin, 25, Cout, Mpad, s, &wpu);
         if (rc) return rc;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_deconv5x5s2_ws_bytes(N, Cin, Cout, Hin, Win)) - gx_kq_amax_ws_floats() : nullptr;
         int xn = 0;

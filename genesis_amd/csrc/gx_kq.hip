@@ -153,32 +153,41 @@ template <> struct QCfg<Q_C5H> {
 template <> struct QCfg<Q_DT0H> : QCfgDTH<0> {};
 template <> struct QCfg<Q_DT1H> : QCfgDTH<1> {};
 typedef __bf16 q_bf16x8 __attribute__((ext_vector_type(8)));
-// fp16 x 3 (template parameter F16 of q_body / q_phase_h; gx_kq_precision(2), DESIGN.md finding 40): every fp32 product from THREE
+// fp16 x 3 (piece form PF_F3 of q_body / q_phase_h; gx_kq_precision(2), DESIGN.md finding 40): every fp32 product from THREE
 // fp16 piece products -- x * 2^sx = hi + lo (11 + 11 significant bits), hi*hi + hi*lo + lo*hi; the dropped lo*lo term is 2^-22 of the
 // product -- instead of six bf16 ones.  sx, sw: per-tensor power-of-two scales from the tensors' largest magnitudes (gx_f16_scale_exp),
 // taken out of the accumulators before the epilogue.  Same LDS layout (the third piece plane stays unused).
 typedef _Float16 q_f16x8 __attribute__((ext_vector_type(8)));
+// Piece forms of the bf16-pipe kernels (template parameter PF): 0 three bf16 pieces, six piece products (gx_kq_precision(1));
+// 1 two fp16 pieces, three piece products (fp16 x 3 above, gx_kq_precision(2)); 2 ONE bf16 piece (gx_kq_precision(3)): every fp32
+// operand rounded once to bf16 (round to nearest even) -- one v_mfma_f32_32x32x16_bf16 per k-step, fp32 accumulation, one input
+// plane and one-piece weight taps in LDS (a third of the bf16 form's), no scale: bf16 has fp32's exponent range.
+enum { PF_B6 = 0, PF_F3 = 1, PF_B1 = 2 };
 constexpr int QH_TAP_BYTES = 3 * 2 * 64 * 16;          // one tap of one 16-channel chunk: 6144 B
 static_assert(QH_TAP_BYTES == 6144, "gx_kq_h_amax_off (gx_common.h) spells this number out");
 // output-channel rows of a workgroup's weight slice and the bytes of one (tap, chunk) of it
-// (NP pieces per value: three bf16 ones, two fp16 ones)
-template <int MODE, bool F16 = false> struct QHLay { static constexpr int ROWS = MODE == Q_C3H ? 32 : 64, NP = F16 ? 2 : 3, TAPB = NP * 2 * ROWS * 16; };
+// (NP pieces per value: three bf16 ones, two fp16 ones, one bf16 one)
+template <int MODE, int PF = PF_B6> struct QHLay {
+    static constexpr int ROWS = MODE == Q_C3H ? 32 : 64, NP = PF == PF_B1 ? 1 : (PF == PF_F3 ? 2 : 3), TAPB = NP * 2 * ROWS * 16;
+};
 
 // one phase on the bf16 pipe: operands of (tap, mi / nj, piece) straight out of LDS
-template <int MODE, int PH, int NCLS, int MI, bool F16 = false>
+template <int MODE, int PH, int NCLS, int MI, int PF = PF_B6>
 __device__ __forceinline__ void q_phase_h(f32x16 (&acc)[NCLS][MI][2], const char* ib, const char* wb, const int plane_bytes,
                                           const int a_lane_b, const int b_lane0_b, const int b_lane1_b, const int HS16) {
     using C = QCfg<MODE>;
+    using L = QHLay<MODE, PF>;
+    constexpr bool F16 = PF == PF_F3;
     constexpr int nt = C::ntaps(PH);
 #pragma unroll
     for (int i = 0; i < nt; ++i) {
         const int toff = (C::ro(PH, i) * HS16 + C::co(PH, i) * 16);
         q_bf16x8 a[MI][3], b[2][3];
 #pragma unroll
-        for (int pc = 0; pc < (F16 ? 2 : 3); ++pc) {
+        for (int pc = 0; pc < L::NP; ++pc) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
-                a[mi][pc] = *reinterpret_cast<const q_bf16x8*>(wb + i * QHLay<MODE, F16>::TAPB + pc * (QHLay<MODE, F16>::TAPB / QHLay<MODE, F16>::NP) + a_lane_b + mi * 512);
+                a[mi][pc] = *reinterpret_cast<const q_bf16x8*>(wb + i * L::TAPB + pc * (L::TAPB / L::NP) + a_lane_b + mi * 512);
             b[0][pc] = *reinterpret_cast<const q_bf16x8*>(ib + pc * plane_bytes + b_lane0_b + toff);
             b[1][pc] = *reinterpret_cast<const q_bf16x8*>(ib + pc * plane_bytes + b_lane1_b + toff);
         }
@@ -191,7 +200,9 @@ __device__ __forceinline__ void q_phase_h(f32x16 (&acc)[NCLS][MI][2], const char
 #if GX_QH_ABL & 4
                 c[0] += (float)a[mi][0][0] * (float)b[nj][0][0] + (float)a[mi][1][1] * (float)b[nj][1][1] + (float)a[mi][2][2] * (float)b[nj][2][2];
 #else
-                if constexpr (F16) {
+                if constexpr (PF == PF_B1) {
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[nj][0], c, 0, 0, 0);
+                } else if constexpr (F16) {
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(q_f16x8, a[mi][1]), __builtin_bit_cast(q_f16x8, b[nj][0]), c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(q_f16x8, a[mi][0]), __builtin_bit_cast(q_f16x8, b[nj][1]), c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(q_f16x8, a[mi][0]), __builtin_bit_cast(q_f16x8, b[nj][0]), c, 0, 0, 0);
@@ -306,11 +317,12 @@ __device__ __forceinline__ float q_amax_parts(const float* __restrict__ parts, i
 // NQ: (position, quad) slots staged per thread per input tile (2 * CHS <= NQ * 256)
 // MI: 32-channel MFMA tiles per wave along M.  2 = the workgroup's whole 64-channel tile; 1 = one half (mh) of it --
 // the last tiles of a grid that does not divide the chip are split into two half-work workgroups (q_split_tail).
-template <int MODE, int NQ, bool STATS, int MI = 2, bool F16 = false, bool TAP = false>
+template <int MODE, int NQ, bool STATS, int MI = 2, int PF = PF_B6, bool TAP = false>
 __device__ __forceinline__ void q_body(const float* __restrict__ in, const float* __restrict__ wp,
                                        const float* __restrict__ bias, float* __restrict__ out, const QGeom& g,
                                        float* lds, const int bx, const int by, const int par_a, const int mh = 0) {
     using C = QCfg<MODE>;
+    constexpr bool F16 = PF == PF_F3, B1 = PF == PF_B1;
     constexpr bool B16 = MODE >= Q_DT0H;               // bf16 matrix pipe, 16-channel chunks (QCfgDTH)
     constexpr int NPH = C::NPH, NT = C::NT, MAXT = C::MAXT, NCLS = C::NCLS;
     constexpr int NW = (MAXT * 128 + 255) / 256;       // float4 weight loads per thread per phase
@@ -344,7 +356,7 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
         const_cast<float*>(in), 0, (int)((unsigned)g.N * (unsigned)g.K * (unsigned)HiWi * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(wp), 0,
-        B16 ? (int)((unsigned)NT * (unsigned)(g.K / 16) * gridDim.y * (unsigned)QHLay<MODE, F16>::TAPB)
+        B16 ? (int)((unsigned)NT * (unsigned)(g.K / 16) * gridDim.y * (unsigned)QHLay<MODE, PF>::TAPB)
             : (int)((unsigned)NT * (unsigned)g.K * gridDim.y * 256u), 0x00020000);
     int voff[NQ];
 #pragma unroll
@@ -378,8 +390,8 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
     if constexpr (B16 && F16) f16_sx = gx_f16_scale_exp(q_amax_parts(g.x_amax, g.x_amax_n));
     if constexpr (B16) {
         // ---- the bf16-pipe pipeline: chunks of 16 channels, phases of <= 3 taps
-        constexpr int TAPB = QHLay<MODE, F16>::TAPB;
-        constexpr int NPL = QHLay<MODE, F16>::NP;                          // input piece planes in LDS
+        constexpr int TAPB = QHLay<MODE, PF>::TAPB;
+        constexpr int NPL = QHLay<MODE, PF>::NP;                           // input piece planes in LDS
         constexpr int NWH = (MAXT * (TAPB / 16) + 255) / 256;              // 16-byte weight pieces per thread per phase
         constexpr int WSLOTB = NWH * 256 * 16;                             // bytes per weight buffer
         // four staging rounds (the 64-pixel-wide tiles of a 64 x 64 base grid: 6 x 66 halo positions): exact planes, so that three
@@ -389,7 +401,7 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
         char* const ibuf = reinterpret_cast<char*>(lds);
         char* const wbufb = ibuf + NPL * plane_bytes;
         const int quad_l = lane >> 5;
-        const int a_lane_b = (quad_l * QHLay<MODE, F16>::ROWS + (lane & 31)) * 16 + mh * 512;   // + mi * 512 + piece * TAPB / 3 + tap * TAPB
+        const int a_lane_b = (quad_l * QHLay<MODE, PF>::ROWS + (lane & 31)) * 16 + mh * 512;    // + mi * 512 + piece * TAPB / NP + tap * TAPB
         int b_lane_b[2];
 #pragma unroll
         for (int nj = 0; nj < 2; ++nj) {
@@ -416,7 +428,9 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
         {                                                                                              \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                           \
                 q_bf16x8 ph_, pm_, pl_;                                                                \
-                if (F16) {                                                                             \
+                if (B1) {                                                                              \
+                    _Pragma("unroll") for (int e = 0; e < 8; ++e) ph_[e] = (__bf16)xin[q][e];          \
+                } else if (F16) {                                                                      \
                     q_f16x8 fh_, fl_;                                                                  \
                     _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                    \
                         const float xs_ = ldexpf(xin[q][e], f16_sx);                                   \
@@ -435,8 +449,8 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
                 char* d_ = ibuf + (tid + q * 256) * 16;                                                \
                 if (!TRIM || tid + q * 256 < 2 * CHS) {                                                \
                 *reinterpret_cast<q_bf16x8*>(d_) = ph_;                                                \
-                *reinterpret_cast<q_bf16x8*>(d_ + plane_bytes) = pm_;                                  \
-                if (!F16) *reinterpret_cast<q_bf16x8*>(d_ + 2 * plane_bytes) = pl_;                    \
+                if (!B1) *reinterpret_cast<q_bf16x8*>(d_ + plane_bytes) = pm_;                         \
+                if (!F16 && !B1) *reinterpret_cast<q_bf16x8*>(d_ + 2 * plane_bytes) = pl_;             \
                 }                                                                                      \
             }                                                                                          \
         }
@@ -482,7 +496,7 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
                 if (more) GX_QH_LOAD_W(last_ph ? sc + 1 : sc, NXT)                                               \
                 if (EARLY_IN) { if ((PH_) == 0 && !last_chunk && !(GX_QH_ABL & 8)) GX_QH_LOAD_IN(sc + 1, 0) }    \
                 else if (in_next) GX_QH_LOAD_IN(last_ph ? sc + 1 : sc, C::plane(NXT))                            \
-                q_phase_h<MODE, (PH_), NCLS, MI, F16>(acc, ibuf, wbufb + (ONE_W ? 0 : (s & 1)) * WSLOTB, plane_bytes, \
+                q_phase_h<MODE, (PH_), NCLS, MI, PF>(acc, ibuf, wbufb + (ONE_W ? 0 : (s & 1)) * WSLOTB, plane_bytes, \
                                                  a_lane_b, b_lane_b[0], b_lane_b[1], HS16);                      \
                 if (ONE_W) {                      /* one weight buffer: everyone is done with it (and the tile) */ \
                     if (more) { __syncthreads(); GX_QH_STORE_W(wbufb) }                                          \
@@ -891,18 +905,18 @@ kq_dt_kernel(const float* __restrict__ in, const float* __restrict__ wp0, const 
     }
 }
 
-template <int NQ, bool F16 = false>
+template <int NQ, int PF = PF_B6>
 __global__ void __launch_bounds__(256, 2)
 kq_dgh_kernel(const float* __restrict__ in, const float* __restrict__ wp, float* __restrict__ out, QGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // (XCD-aware tile map over the whole-tile workgroups: neighbouring tiles, which share halo rows, on one XCD's L2)
     const int bx = (int)blockIdx.x < g.nfull ? gx_xcd_tile(blockIdx.x, g.nfull) : (int)blockIdx.x;
-    if (bx < g.nfull) q_body<Q_DGH, NQ, false, 2, F16>(in, wp, nullptr, out, g, lds, bx, blockIdx.y, 0);
-    else q_body<Q_DGH, NQ, false, 1, F16>(in, wp, nullptr, out, g, lds, g.nfull + ((bx - g.nfull) >> 1), blockIdx.y, 0, (bx - g.nfull) & 1);
+    if (bx < g.nfull) q_body<Q_DGH, NQ, false, 2, PF>(in, wp, nullptr, out, g, lds, bx, blockIdx.y, 0);
+    else q_body<Q_DGH, NQ, false, 1, PF>(in, wp, nullptr, out, g, lds, g.nfull + ((bx - g.nfull) >> 1), blockIdx.y, 0, (bx - g.nfull) & 1);
 }
 
 // conv3x3 on the bf16 pipe, 32 output channels per workgroup (blockIdx.y)
-template <int NQ, bool F16 = false, bool TAP = false>
+template <int NQ, int PF = PF_B6, bool TAP = false>
 __global__ void __launch_bounds__(256, 3)
 kq_c3h_kernel(const float* __restrict__ in, const float* __restrict__ wp, const float* __restrict__ bias,
               float* __restrict__ out, QGeom g) {
@@ -917,7 +931,7 @@ kq_c3h_kernel(const float* __restrict__ in, const float* __restrict__ wp, const 
     // two 16-channel chunks per tile that tail is a large part of a tile's life
     for (int t = blockIdx.x; t < g.nfull; t += gridDim.x) {
         const int tile = gx_xcd_tile(t, g.nfull);
-        q_body<Q_C3H, NQ, false, 1, F16, TAP>(in, wp, bias, out, g, lds, tile, blockIdx.y, 0, 0);
+        q_body<Q_C3H, NQ, false, 1, PF, TAP>(in, wp, bias, out, g, lds, tile, blockIdx.y, 0, 0);
         __syncthreads();          // the next tile's staging overwrites LDS the slowest wave may still be reading
     }
     if constexpr (TAP) {          // one partial maximum per workgroup for the tensor's next reader
@@ -927,15 +941,15 @@ kq_c3h_kernel(const float* __restrict__ in, const float* __restrict__ wp, const 
 }
 
 // 5 x 5 stride-1 conv on the bf16 pipe: 16 x 16-pixel tiles (20 x 20 halo positions: four staging rounds, exact LDS planes)
-template <int NQ, bool F16 = false>
+template <int NQ, int PF = PF_B6>
 __global__ void __launch_bounds__(256, 2)
 kq_c5h_kernel(const float* __restrict__ in, const float* __restrict__ wp, float* __restrict__ out, QGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    q_body<Q_C5H, NQ, false, 2, F16>(in, wp, nullptr, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y, 0);
+    q_body<Q_C5H, NQ, false, 2, PF>(in, wp, nullptr, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y, 0);
 }
 
 // the same launch shape on the bf16 matrix pipe (Q_DT0H / Q_DT1H)
-template <int NQ, bool STATS, bool F16 = false>
+template <int NQ, bool STATS, int PF = PF_B6>
 __global__ void __launch_bounds__(256, 2)
 kq_dth_kernel(const float* __restrict__ in, const float* __restrict__ wp0, const float* __restrict__ wp1,
               const float* __restrict__ bias, float* __restrict__ out, QGeom g) {
@@ -953,12 +967,12 @@ kq_dth_kernel(const float* __restrict__ in, const float* __restrict__ wp0, const
     // (XCD-aware tile map over the whole-tile workgroups: neighbouring tiles, which share halo rows, on one XCD's L2)
     const int bx = bxr < g.nfull ? gx_xcd_tile(bxr, g.nfull) : bxr;
     if (bx < g.nfull) {
-        if (z) q_body<Q_DT1H, NQ, STATS, 2, F16>(in, wp1, bias, out, g, lds, bx, blockIdx.y, 1);
-        else q_body<Q_DT0H, NQ, STATS, 2, F16>(in, wp0, bias, out, g, lds, bx, blockIdx.y, 0);
+        if (z) q_body<Q_DT1H, NQ, STATS, 2, PF>(in, wp1, bias, out, g, lds, bx, blockIdx.y, 1);
+        else q_body<Q_DT0H, NQ, STATS, 2, PF>(in, wp0, bias, out, g, lds, bx, blockIdx.y, 0);
     } else {
         const int tile = g.nfull + ((bx - g.nfull) >> 1), mh = (bx - g.nfull) & 1;
-        if (z) q_body<Q_DT1H, NQ, STATS, 1, F16>(in, wp1, bias, out, g, lds, tile, blockIdx.y, 1, mh);
-        else q_body<Q_DT0H, NQ, STATS, 1, F16>(in, wp0, bias, out, g, lds, tile, blockIdx.y, 0, mh);
+        if (z) q_body<Q_DT1H, NQ, STATS, 1, PF>(in, wp1, bias, out, g, lds, tile, blockIdx.y, 1, mh);
+        else q_body<Q_DT0H, NQ, STATS, 1, PF>(in, wp0, bias, out, g, lds, tile, blockIdx.y, 0, mh);
     }
 }
 
@@ -1088,12 +1102,16 @@ int gx_kq_deconv_fwd_launch(const float* in, const float* wp0, const float* wp1,
 static int g_kq_h = -1;     // 1 (default): eligible layers run there; GENESIS_KQ_BF16X6=0 / gx_kq_precision(0): fp32 pipe
 static void kq_h_init() {
     if (g_kq_h >= 0) return;
+    const int lv = gx_env_matmul_level();               // GENESIS_MATMUL_PRECISION decides ahead of the per-family variables
+    if (lv >= 0) { g_kq_h = gx_matmul_level_mode(lv); return; }
     const char* e = getenv("GENESIS_KQ_BF16X6");
     const char* f = getenv("GENESIS_KQ_F16X3");         // 0: six bf16 piece products instead of three fp16 ones (finding 40)
     g_kq_h = (e && e[0] == '0') ? 0 : ((f && f[0] == '0') ? 1 : 2);
 }
 static bool kq_h_on() { kq_h_init(); return g_kq_h != 0; }
 bool gx_kq_f16_on() { kq_h_init(); return g_kq_h == 2; }
+bool gx_kq_b1_on() { kq_h_init(); return g_kq_h == 3; }
+int gx_kq_mode_now() { kq_h_init(); return g_kq_h; }
 
 // ---- largest magnitude of a tensor, for the fp16 x 3 form's power-of-two scale: ONE launch of kAmaxParts workgroups (1024 threads:
 //      16 waves per CU keep the HBM busy) writes kAmaxParts partial maxima; the conv kernels reduce them themselves (one 16-byte load
@@ -1197,10 +1215,10 @@ size_t gx_kq_deconv_h_pack_bytes(int K, int M, int nt) {     // one row parity's
 }
 // LDS of the bf16-pipe transposed-conv kernels: three input piece planes (exact at four staging rounds) + two weight buffers;
 // 0: the tile does not leave room for two workgroups per CU
-// (f16: the launch's allocation in the fp16 x 3 form -- two planes, two-piece weight taps: 48 KB at three staging rounds, i.e. THREE
-//  workgroups per CU where the registers allow it (kq_dgh_kernel<3, true>: 156); eligibility is always decided on the three-piece size)
-static size_t qh_lds(const QGeom& g, int nq, bool f16 = false) {
-    const int np = f16 ? 2 : 3;
+// (np < 3: the launch's allocation in the fp16 x 3 form -- two planes, two-piece weight taps: 48 KB at three staging rounds, i.e. THREE
+//  workgroups per CU where the registers allow it (kq_dgh_kernel<3, PF_F3>: 156) -- or the one-piece form (one plane, one-piece taps);
+//  eligibility is always decided on the three-piece size: every form covers the same layers)
+static size_t qh_lds(const QGeom& g, int nq, int np = 3) {
     const int NWH = (3 * (np * 2048 / 16) + 255) / 256;
     const int CHS = (1 << g.lG) * ((1 << g.lTH) + 2) * ((1 << g.lTW) + 2);
     const size_t planes = nq == 4 ? (size_t)np * 2 * CHS * 16 : (size_t)np * nq * 256 * 16;
@@ -1221,7 +1239,8 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
     if (!q_plan(N, K, M, Hb, Wb, Hb, Wb, 2 * Hb, 2 * Wb, &g, &nq, &lds, 5) || qh_lds(g, nq) == 0 || K % 16 != 0) {
         gx_set_error("kq deconv fwd (bf16 pipe): shape not eligible"); return GX_EINVAL;
     }
-    lds = qh_lds(g, nq, amax_ws != nullptr);
+    const bool b1 = gx_kq_b1_on() && !amax_ws;          // one bf16 piece (packs 62 / 63)
+    lds = qh_lds(g, nq, b1 ? 1 : (amax_ws ? 2 : 3));
     const bool st = stats && g.lG == 0 && (M % 8) == 0;
     if (stats_parts) *stats_parts = 0;
     if (st) {
@@ -1238,7 +1257,7 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
     {
         GxProf pf(KID_KQ_DTH, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * Hb * Wb + (double)N * M * 4 * Hb * Wb + 25.0 * K * M));
-        static bool a[8] = {false, false, false, false, false, false, false, false};
+        static bool a[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
         if (amax_ws) {          // fp16 x 3: the input's amax (one small launch ahead of this one, outside its profiling record)
             g.x_amax = x_parts ? x_parts : amax_ws;
             if (x_parts) g.x_amax_n = x_nparts;
@@ -1247,6 +1266,11 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
             else if (nq == 3) { q_set_attr(&kq_dth_kernel<3, false, true>, &a[5]); hipLaunchKernelGGL((kq_dth_kernel<3, false, true>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
             else if (st) { q_set_attr(&kq_dth_kernel<4, true, true>, &a[6]); hipLaunchKernelGGL((kq_dth_kernel<4, true, true>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
             else { q_set_attr(&kq_dth_kernel<4, false, true>, &a[7]); hipLaunchKernelGGL((kq_dth_kernel<4, false, true>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
+        } else if (b1) {
+            if (nq == 3 && st) { q_set_attr(&kq_dth_kernel<3, true, PF_B1>, &a[8]); hipLaunchKernelGGL((kq_dth_kernel<3, true, PF_B1>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
+            else if (nq == 3) { q_set_attr(&kq_dth_kernel<3, false, PF_B1>, &a[9]); hipLaunchKernelGGL((kq_dth_kernel<3, false, PF_B1>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
+            else if (st) { q_set_attr(&kq_dth_kernel<4, true, PF_B1>, &a[10]); hipLaunchKernelGGL((kq_dth_kernel<4, true, PF_B1>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
+            else { q_set_attr(&kq_dth_kernel<4, false, PF_B1>, &a[11]); hipLaunchKernelGGL((kq_dth_kernel<4, false, PF_B1>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
         } else
         if (nq == 3 && st) { q_set_attr(&kq_dth_kernel<3, true>, &a[0]); hipLaunchKernelGGL((kq_dth_kernel<3, true>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
         else if (nq == 3) { q_set_attr(&kq_dth_kernel<3, false>, &a[1]); hipLaunchKernelGGL((kq_dth_kernel<3, false>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
@@ -1296,8 +1320,13 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
     const float* x_parts = nullptr; int x_nparts = 0;
     if (!q_plan_c3h(N, K, M, H, W, &g, &nq, &lds)) { gx_set_error("kq conv3x3 (bf16 pipe): shape not eligible"); return GX_EINVAL; }
     g.act = act; g.mask = mask; g.mask_act = mask_act;
+    const bool b1 = gx_kq_b1_on() && !amax_ws;           // one bf16 piece (packs 60 / 61)
+    if (b1) {
+        constexpr int NW1 = (3 * (QHLay<Q_C3H, PF_B1>::TAPB / 16) + 255) / 256;
+        lds = (size_t)nq * 256 * 16 + (size_t)NW1 * 256 * 16;             // one input plane + one one-piece weight buffer
+    }
     if (amax_ws) {
-        constexpr int NWF = (3 * (QHLay<Q_C3H, true>::TAPB / 16) + 255) / 256;
+        constexpr int NWF = (3 * (QHLay<Q_C3H, PF_F3>::TAPB / 16) + 255) / 256;
         lds = (size_t)2 * nq * 256 * 16 + (size_t)NWF * 256 * 16;          // two input piece planes + one two-piece weight buffer
         // the input's partial maxima handed in by the caller (gx_conv_input_amax: the norm kernel that wrote it), else a pass of our own
         int rc = kq_hint_parts(&x_parts, &x_nparts, amax_ws, s); if (rc) return rc;
@@ -1314,8 +1343,11 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
     {
         GxProf pf(KID_KQ_C3H, s, 2.0 * N * (double)M * K * 9 * H * W,
                   4.0 * ((double)N * K * H * W + (double)N * M * H * W + 9.0 * K * M));
-        static bool a3 = false, a4 = false, f3 = false, f4 = false;
-        if (amax_ws) {          // fp16 x 3 (packs 40 / 41)
+        static bool a3 = false, a4 = false, f3 = false, f4 = false, b3 = false, b4 = false;
+        if (b1) {
+            if (nq == 3) { q_set_attr(&kq_c3h_kernel<3, PF_B1>, &b3); hipLaunchKernelGGL((kq_c3h_kernel<3, PF_B1>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
+            else { q_set_attr(&kq_c3h_kernel<4, PF_B1>, &b4); hipLaunchKernelGGL((kq_c3h_kernel<4, PF_B1>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
+        } else if (amax_ws) {          // fp16 x 3 (packs 40 / 41)
             g.x_amax = x_parts ? x_parts : amax_ws; g.w_amax = w_amax;
             if (x_parts) g.x_amax_n = x_nparts;
             static bool t3 = false, t4 = false;
@@ -1359,8 +1391,13 @@ int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K,
                      float* amax_ws, const float* w_amax, const float* x_parts, int x_nparts) {
     QGeom g; size_t lds;
     if (!q_plan_c5h(N, K, M, H, W, &g, &lds)) { gx_set_error("kq conv5x5 (bf16 pipe): shape not eligible"); return GX_EINVAL; }
+    const bool b1 = gx_kq_b1_on() && !amax_ws;           // one bf16 piece (packs 67 / 68)
+    if (b1) {
+        constexpr int NW1 = (3 * (QHLay<Q_C5H, PF_B1>::TAPB / 16) + 255) / 256;
+        lds = (size_t)2 * (20 * 20) * 16 + (size_t)2 * NW1 * 256 * 16;
+    }
     if (amax_ws) {
-        constexpr int NWF = (3 * (QHLay<Q_C5H, true>::TAPB / 16) + 255) / 256;
+        constexpr int NWF = (3 * (QHLay<Q_C5H, PF_F3>::TAPB / 16) + 255) / 256;
         lds = (size_t)2 * 2 * (20 * 20) * 16 + (size_t)2 * NWF * 256 * 16;
         // (x_parts: the input's partial maxima from the kernel that wrote it -- no pass of our own)
         if (!x_parts) { const int rc = gx_kq_amax_launch(in, (size_t)N * K * H * W, amax_ws, s); if (rc) return rc; }
@@ -1369,8 +1406,11 @@ int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K,
     dim3 grid(g.nfull, gx_ceil_div(M, 64));
     {
         GxProf pf(KID_KQ_C5H, s, 2.0 * N * (double)M * K * 25 * H * W, 4.0 * ((double)N * K * H * W + (double)N * M * H * W + 25.0 * K * M));
-        static bool a4 = false, f4 = false;
-        if (amax_ws) {          // fp16 x 3 (packs 47 / 48)
+        static bool a4 = false, f4 = false, b4 = false;
+        if (b1) {
+            q_set_attr(&kq_c5h_kernel<4, PF_B1>, &b4);
+            hipLaunchKernelGGL((kq_c5h_kernel<4, PF_B1>), grid, dim3(256), lds, s, in, wp, out, g);
+        } else if (amax_ws) {          // fp16 x 3 (packs 47 / 48)
             g.x_amax = x_parts ? x_parts : amax_ws; g.w_amax = w_amax;
             if (x_parts) g.x_amax_n = x_nparts;
             q_set_attr(&kq_c5h_kernel<4, true>, &f4);
@@ -1395,7 +1435,8 @@ int gx_kq_deconv_dgrad_h_launch(const float* dy, const float* wp, float* dx, int
     if (!q_plan(N, K, M, Hb, Wb, 2 * Hb, 2 * Wb, Hb, Wb, &g, &nq, &lds, 9) || qh_lds(g, nq) == 0 || K % 16 != 0) {
         gx_set_error("kq deconv dgrad (bf16 pipe): shape not eligible"); return GX_EINVAL;
     }
-    lds = qh_lds(g, nq, amax_ws != nullptr);
+    const bool b1 = gx_kq_b1_on() && !amax_ws;          // one bf16 piece (pack 64)
+    lds = qh_lds(g, nq, b1 ? 1 : (amax_ws ? 2 : 3));
     if (amax_ws && !x_parts) { const int rc = gx_kq_amax_launch(dy, (size_t)N * K * 4 * Hb * Wb, amax_ws, s); if (rc) return rc; }
     else if (amax_ws) { const int rc = kq_fold_parts(&x_parts, &x_nparts, amax_ws, s); if (rc) return rc; }
     dim3 grid(1, gx_ceil_div(M, 64));
@@ -1403,8 +1444,11 @@ int gx_kq_deconv_dgrad_h_launch(const float* dy, const float* wp, float* dx, int
     {
         GxProf pf(KID_KQ_DGH, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * 4 * Hb * Wb + (double)N * M * Hb * Wb + 25.0 * K * M));
-        static bool a3 = false, a4 = false, f3 = false, f4 = false;
-        if (amax_ws) {
+        static bool a3 = false, a4 = false, f3 = false, f4 = false, b3 = false, b4 = false;
+        if (b1) {
+            if (nq == 3) { q_set_attr(&kq_dgh_kernel<3, PF_B1>, &b3); hipLaunchKernelGGL((kq_dgh_kernel<3, PF_B1>), grid, dim3(256), lds, s, dy, wp, dx, g); }
+            else { q_set_attr(&kq_dgh_kernel<4, PF_B1>, &b4); hipLaunchKernelGGL((kq_dgh_kernel<4, PF_B1>), grid, dim3(256), lds, s, dy, wp, dx, g); }
+        } else if (amax_ws) {
             g.x_amax = x_parts ? x_parts : amax_ws;
             if (x_parts) g.x_amax_n = x_nparts;
             g.w_amax = w_amax;
@@ -1437,8 +1481,8 @@ int gx_kq_deconv_dgrad_launch(const float* dy, const float* wp, float* dx, int N
 }
 
 extern "C" int gx_kq_precision(int mode) {
-    GX_CHECK_ARG(mode >= -1 && mode <= 2, "gx_kq_precision: mode must be 0 (fp32 matrix pipe), 1 (bf16 pipe, six piece products), 2 (as 1, the transposed convs from three fp16 piece products) or -1 (the environment's default)");
-    g_kq_h = mode;        // (-1: kq_h_init reads GENESIS_KQ_BF16X6 / GENESIS_KQ_F16X3 again)
+    GX_CHECK_ARG(mode >= -1 && mode <= 3, "gx_kq_precision: mode must be 0 (fp32 matrix pipe), 1 (bf16 pipe, six piece products), 2 (as 1, the transposed convs from three fp16 piece products), 3 (as 1, one bf16 piece per operand) or -1 (the environment's default)");
+    g_kq_h = mode;        // (-1: kq_h_init reads GENESIS_MATMUL_PRECISION / GENESIS_KQ_BF16X6 / GENESIS_KQ_F16X3 again)
     return GX_OK;
 }
 

@@ -226,7 +226,8 @@ __device__ __forceinline__ f32x16 wq_mma6(const WqB3& a, const WqB3& b, f32x16 c
     return c;
 }
 
-template <int CLS, int LTW, int NI>
+// B1: the one-piece form (gx_wgq_precision(3)): every operand rounded once to bf16 (round to nearest even), ONE MFMA per 16 pixels and tap
+template <int CLS, int LTW, int NI, bool B1 = false>
 __device__ __forceinline__ void wq_tile_b6(const float* __restrict__ rd, float* __restrict__ wr,
                                            f32x16 (&acc)[WqTap<CLS>::NT], const WqW& w, const int (&goff)[NI],
                                            const int (&info)[NI], const int img, const int th, const int tw,
@@ -250,13 +251,20 @@ __device__ __forceinline__ void wq_tile_b6(const float* __restrict__ rd, float* 
 #pragma unroll
             for (int e = 0; e < 4; ++e) av[4 * p + e] = t4[e];
         }
+        WqB3 a3[SA];                                  // [column parity]
+        if constexpr (B1) {
+#pragma unroll
+            for (int pb = 0; pb < SA; ++pb)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) a3[pb].h[i] = (__bf16)av[SA * i + pb];
+        } else {
         __bf16 ah[8 * SA], am[8 * SA], al[8 * SA];
         wq_split<8 * SA>(av, ah, am, al);
-        WqB3 a3[SA];                                  // [column parity]
 #pragma unroll
         for (int pb = 0; pb < SA; ++pb)
 #pragma unroll
             for (int i = 0; i < 8; ++i) { a3[pb].h[i] = ah[SA * i + pb]; a3[pb].m[i] = am[SA * i + pb]; a3[pb].l[i] = al[SA * i + pb]; }
+        }
 #pragma unroll
         for (int rr = 0; rr < NRO; ++rr) {
             // B: halo columns c_ - 1 .. c_ + 8 of row r_ + RO0 + rr (window of 10 floats; conv3x3 offsets 0..2, the
@@ -269,6 +277,20 @@ __device__ __forceinline__ void wq_tile_b6(const float* __restrict__ rd, float* 
             bv[9] = rd[w.b_base + (((qb + 3) ^ w.b_f) << 2)];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { bv[1 + e] = m0[e]; bv[5 + e] = m1[e]; }
+            if constexpr (B1) {
+                __bf16 bh[10];
+#pragma unroll
+                for (int e = 0; e < 10; ++e) bh[e] = (__bf16)bv[e];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if (WT::ro(t) - RO0 != rr) continue;
+                    gx_bf16x8 b1;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) b1[i] = bh[WT::co(t) + i];
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[WT::pb(t)].h, b1, acc[t], 0, 0, 0);
+                }
+                continue;
+            }
             __bf16 bh[10], bm[10], bl[10];
             wq_split<10>(bv, bh, bm, bl);
 #pragma unroll
@@ -285,8 +307,9 @@ __device__ __forceinline__ void wq_tile_b6(const float* __restrict__ rd, float* 
 // in registers and written as one slab (`slab` points at [tap 0][row 0][col 0] of this workgroup's block; rows are ldc
 // floats apart, taps tstride).  The grouped kernel hands a workgroup one strided segment, the stream-K kernel one or
 // more contiguous ones.
-// B6: the tiles run on the bf16 matrix pipe (wq_tile_b6: fp32 products from six bf16 piece products) instead of the fp32 one
-template <int CLS, int LTW, bool B6>
+// B6: the tiles run on the bf16 matrix pipe (wq_tile_b6: fp32 products from six bf16 piece products) instead of the fp32 one;
+// B1 (with B6): from one bf16 piece per operand
+template <int CLS, int LTW, bool B6, bool B1 = false>
 __device__ __forceinline__ void wq_segment(const float* a, const float* b, const float* zeros, float* lds, int CA, int CB,
                                            int ca0, int cb0, int Hb, int Wb, int tiles_h, int tiles_w, int t0, int tstep,
                                            int tend, float* slab, int ldc, int tstride) {
@@ -366,7 +389,7 @@ __device__ __forceinline__ void wq_segment(const float* a, const float* b, const
         if (t_tw >= tiles_w) { t_tw -= tiles_w; ++t_th; }
         if (t_th >= tiles_h) { t_th -= tiles_h; ++t_img; }
         if (B6)
-            wq_tile_b6<CLS, LTW, NI>(lds + (it & 1) * STAGE, lds + ((it + 1) & 1) * STAGE, acc, w, goff, info, t_img, t_th,
+            wq_tile_b6<CLS, LTW, NI, B1>(lds + (it & 1) * STAGE, lds + ((it + 1) & 1) * STAGE, acc, w, goff, info, t_img, t_th,
                                      t_tw, tile + tstep < tend);
         else
             wq_tile<CLS, LTW, NI>(lds + (it & 1) * STAGE, lds + ((it + 1) & 1) * STAGE, acc, w, goff, info, t_img, t_th,
@@ -425,12 +448,17 @@ typedef const __attribute__((address_space(1))) f32x4* gx_gptr4;
 // the kernels that wrote the tensors: gx_wgq_operand_amax) instead of three bf16 ones -- hi*hi + hi*lo + lo*hi, three MFMAs per 16
 // pixels and tap instead of six (findings 40 and 42), two piece planes in LDS instead of three, a 24-VALU split
 // per octet instead of 44; the accumulators are scaled back by 2^-(eA + eB) when the slab is written.
+// B1 (WC += 200000, gx_wgq_precision(3)): ONE bf16 piece per value (round to nearest even) -- one MFMA per 16 pixels and tap, one piece
+// plane per operand in LDS, a 2-piece split per octet (pack | store), no scale.  The tile keeps three slots per tap (NSLT): the slots
+// without an MFMA carry the staging pieces as before -- the schedule of the fp16 tile with two of its three MFMAs left out.
 template <int CLS, int WC> struct WrGeo {
-    static constexpr bool F16 = WC >= 100000;
+    static constexpr bool B1 = WC >= 200000;
+    static constexpr bool F16 = WC >= 100000 && !B1;
     static constexpr int HF = (WC / 1000) % 100, W = WC % 1000;
-    static constexpr int NPL = F16 ? 2 : 3;                    // piece planes per operand
-    static constexpr int NTERM = F16 ? 3 : 6;                  // piece products per fp32 product
-    static constexpr int SPQ = F16 ? 6 : 14;                   // split pieces (slots) per octet
+    static constexpr int NPL = B1 ? 1 : (F16 ? 2 : 3);         // piece planes per operand
+    static constexpr int NTERM = B1 ? 1 : (F16 ? 3 : 6);       // piece products per fp32 product
+    static constexpr int NSLT = B1 ? 3 : NTERM;                // slots per tap (MFMA + piece; B1: the MFMA in the first)
+    static constexpr int SPQ = B1 ? 2 : (F16 ? 6 : 14);        // split pieces (slots) per octet
     static constexpr int KS = HF == 3 ? 4 : (HF ? 2 : 1);
     using WT = WqTap<CLS>;
     static constexpr int SA = WT::SA, NPB = WT::NPB, NT = WT::NT, NRO = WT::NRO, RO0 = WT::RO0;
@@ -514,6 +542,13 @@ __device__ __forceinline__ void wr_split_f16_pair(float v0, float v1, float sc, 
 __device__ __forceinline__ void wr_split8_f16(const float (&v)[8], float sc, gx_u32x4& ph, gx_u32x4& pl) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) { unsigned h, l; wr_split_f16_pair(v[2 * i], v[2 * i + 1], sc, h, l); ph[i] = h; pl[i] = l; }
+}
+// 8 fp32 values -> ONE bf16 piece each, rounded to nearest even (the one-piece form)
+__device__ __forceinline__ gx_u32x4 wr_pk8(const float (&v)[8]) {
+    gx_bf16x8 b;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) b[i] = (__bf16)v[i];
+    return __builtin_bit_cast(gx_u32x4, b);
 }
 
 // per-thread constants of a segment
@@ -606,7 +641,9 @@ __device__ __forceinline__ void wr_store(char* lds, const WrT<CLS, W>& w, int ab
                 for (int i = 0; i < 8; ++i) v[i] = pa[j][(SA * i + par) >> 2][(SA * i + par) & 3];   // de-interleave the column parities
                 gx_u32x4 ph, pm, pl;
                 char* d = lds + abuf + par * G::NPL * G::A_PLANE + w.stA[j];
-                if constexpr (G::F16) {
+                if constexpr (G::B1) {
+                    *reinterpret_cast<gx_u32x4*>(d) = wr_pk8(v);
+                } else if constexpr (G::F16) {
                     wr_split8_f16(v, w.scA, ph, pm);
                     *reinterpret_cast<gx_u32x4*>(d) = ph;
                     *reinterpret_cast<gx_u32x4*>(d + G::A_PLANE) = pm;
@@ -624,7 +661,9 @@ __device__ __forceinline__ void wr_store(char* lds, const WrT<CLS, W>& w, int ab
             for (int i = 0; i < 8; ++i) v[i] = pb[j][i >> 2][i & 3];
             gx_u32x4 ph, pm, pl;
             char* d = lds + G::RING0 + bslot + w.stB[j];
-            if constexpr (G::F16) {
+            if constexpr (G::B1) {
+                *reinterpret_cast<gx_u32x4*>(d) = wr_pk8(v);
+            } else if constexpr (G::F16) {
                 wr_split8_f16(v, w.scB, ph, pm);
                 *reinterpret_cast<gx_u32x4*>(d) = ph;
                 *reinterpret_cast<gx_u32x4*>(d + G::B_PLANE) = pm;
@@ -664,7 +703,7 @@ template <int CLS, int W> struct WrSched {
     static constexpr int NU = NG * NRO;                       // units per tile
     static constexpr int NCO = G::NT / NRO;                   // taps per unit
     static constexpr int NPL = G::NPL;
-    static constexpr int NMF = G::NTERM * NCO;                // MFMAs (slots) per unit
+    static constexpr int NMF = G::NSLT * NCO;                 // slots per unit (MFMAs: NTERM * NCO of them)
     static constexpr int NOCT = G::UPT * (NPB + 1);           // octets this thread splits per tile
     static constexpr int NQ = G::SPQ * NOCT + (G::NS > 1 ? 3 : 0); // split pieces (strips: + the seam value's split | split | stores)
     static constexpr int NFE = 2 * G::UPT + (G::NS > 1 ? 1 : 0);   // fetch pieces (unit 0): the dy / x loads of unit j (+ the seam load)
@@ -734,6 +773,10 @@ __device__ __forceinline__ void wr_split_piece(char* lds, const WrT<CLS, W>& w, 
     constexpr int SA = G::SA, NPB = G::NPB;
     if constexpr (Q >= G::SPQ * G::UPT * (NPB + 1)) {      // strips: the seam value (r[0..1], hp[0..2] are free by now)
         constexpr int step = Q - G::SPQ * G::UPT * (NPB + 1);
+        if constexpr (G::B1) {
+            if constexpr (step == 0) st.hp[0] = __builtin_bit_cast(unsigned short, (__bf16)st.sv);
+            else if constexpr (step == 2) *reinterpret_cast<unsigned short*>(lds + anxt + w.stS) = (unsigned short)st.hp[0];
+        } else
         if constexpr (G::F16) {
             if constexpr (step == 0) {
                 st.r[0] = st.sv * w.scA;
@@ -767,6 +810,16 @@ __device__ __forceinline__ void wr_split_piece(char* lds, const WrT<CLS, W>& w, 
     float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = isA ? pa[j][(SA * i + k) >> 2][(SA * i + k) & 3] : pb[j][i >> 2][i & 3];
+    if constexpr (G::B1) {
+        // one bf16 piece: step 0 the four packed conversions, step 1 the store
+        if constexpr (step == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) st.hp[i] = wr_pk(v[2 * i], v[2 * i + 1]);
+        } else {
+            char* d = isA ? lds + anxt + k * G::NPL * G::A_PLANE + w.stA[j] : lds + G::RING0 + bnew + w.stB[j];
+            *reinterpret_cast<gx_u32x4*>(d) = gx_u32x4{st.hp[0], st.hp[1], st.hp[2], st.hp[3]};
+        }
+    } else
     if constexpr (G::F16) {
         // fp16 pieces: steps 0..3 one PAIR each (scale | mask | residual | two packed conversions: 6 VALU), 4 / 5 the two stores
         if constexpr (step < 4) {
@@ -844,8 +897,8 @@ __device__ __forceinline__ void wr_read_b(const char* lds, const WrT<CLS, W>& w,
     using G = WrGeo<CLS, W>;
     const char* p = lds + G::RING0 + (zr ? G::B_ZERO : bs + w.b_rd[g]);
     b3.h = wr_bf(*reinterpret_cast<const gx_u32x4*>(p));
-    b3.m = wr_bf(*reinterpret_cast<const gx_u32x4*>(p + G::B_PLANE));
-    if constexpr (!G::F16) b3.l = wr_bf(*reinterpret_cast<const gx_u32x4*>(p + 2 * G::B_PLANE));
+    if constexpr (G::NPL >= 2) b3.m = wr_bf(*reinterpret_cast<const gx_u32x4*>(p + G::B_PLANE));
+    if constexpr (G::NPL == 3) b3.l = wr_bf(*reinterpret_cast<const gx_u32x4*>(p + 2 * G::B_PLANE));
 }
 
 // fetch piece i: the dy (i even) / x (i odd) loads of load unit i / 2
@@ -918,6 +971,9 @@ __device__ __forceinline__ void wr_slot(char* lds, const WrT<CLS, W>& w, const W
         const gx_bf16x8 ao = G::F16 ? (term == 0 ? a3.m : a3.h) : (term == 0 ? a3.m : (term == 1 ? a3.l : (term == 3 ? a3.m : a3.h)));
         const gx_bf16x8 bo = G::F16 ? (term == 1 ? b3.m : b3.h) : (term == 0 ? b3.m : (term == 2 ? b3.l : (term == 4 ? b3.m : b3.h)));
 #if !(GX_WR_ABL & 1)
+        if constexpr (G::B1) {
+            if constexpr (term == 0) acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3.h, b3.h, acc[tap], 0, 0, 0);
+        } else
         if constexpr (G::F16)
             acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gx_f16x8, ao), __builtin_bit_cast(gx_f16x8, bo), acc[tap], 0, 0, 0);
         else
@@ -1056,7 +1112,8 @@ __device__ __forceinline__ void wr_segment(const float* a, const float* b, const
     if constexpr (G::NS > 1) {
         __syncthreads();      // (the seam bytes lie inside the pieces the fill above zeroes)
         unsigned short sb[3];
-        if constexpr (G::F16) wr_seam_split_f16(wr_seam_load<CLS, W>(w, t0), w.scA, sb);
+        if constexpr (G::B1) { sb[0] = __builtin_bit_cast(unsigned short, (__bf16)wr_seam_load<CLS, W>(w, t0)); sb[1] = sb[2] = 0; }
+        else if constexpr (G::F16) wr_seam_split_f16(wr_seam_load<CLS, W>(w, t0), w.scA, sb);
         else wr_seam_split(wr_seam_load<CLS, W>(w, t0), sb);
         wr_seam_store<CLS, W>(lds, w, 0, sb);
     }
@@ -1144,7 +1201,7 @@ __device__ __attribute__((noinline)) void wr_segment_call(const float* a, const 
 }
 
 // ---- grouped launch: the jobs of one (class, tile width), every workgroup one strided segment
-template <int CLS, int LTW, bool B6>
+template <int CLS, int LTW, bool B6, bool B1 = false>
 __global__ void __launch_bounds__(256, 1)
 wgq_kernel(const WqTable tab, const float* __restrict__ zeros) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1157,7 +1214,7 @@ wgq_kernel(const WqTable tab, const float* __restrict__ zeros) {
     const int nsp = jb.nsplit;
     const int blk = local / nsp, sp = local - blk * nsp;
     const int ca0 = (blk / jb.nbt) * 64, cb0 = (blk % jb.nbt) * 64;
-    wq_segment<CLS, LTW, B6>(jb.a, jb.b, zeros, lds, jb.CA, jb.CB, ca0, cb0, jb.Hb, jb.Wb, jb.tiles_h, jb.tiles_w, sp, nsp,
+    wq_segment<CLS, LTW, B6, B1>(jb.a, jb.b, zeros, lds, jb.CA, jb.CB, ca0, cb0, jb.Hb, jb.Wb, jb.tiles_h, jb.tiles_w, sp, nsp,
                          jb.ntiles, jb.partial + ((size_t)sp * jb.Ttot * jb.CApad + ca0) * jb.CBpad + cb0, jb.CBpad,
                          jb.CApad * jb.CBpad);
 }
@@ -1186,12 +1243,12 @@ struct WsTable { long long U; int njobs, G; long long* times; WsJob job[kMaxSJob
 // allocator ~1.5 KB of scratch per lane; as separate functions each keeps the allocation of its own grouped kernel.
 // The LDS stage pointer is re-derived from the dynamic LDS symbol inside (a pointer parameter would arrive as a flat
 // pointer and turn every ds_read into a flat load).
-template <int CLS, int LTW, bool B6>
+template <int CLS, int LTW, bool B6, bool B1 = false>
 __device__ __attribute__((noinline)) void wq_segment_call(const float* a, const float* b, const float* zeros, int CA, int CB,
                                                           int ca0, int cb0, int Hb, int Wb, int tiles_h, int tiles_w, int t0,
                                                           int t1, float* slab) {
     extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
-    wq_segment<CLS, LTW, B6>(a, b, zeros, lds_dyn, CA, CB, ca0, cb0, Hb, Wb, tiles_h, tiles_w, t0, 1, t1, slab, 64, 4096);
+    wq_segment<CLS, LTW, B6, B1>(a, b, zeros, lds_dyn, CA, CB, ca0, cb0, Hb, Wb, tiles_h, tiles_w, t0, 1, t1, slab, 64, 4096);
 }
 
 __host__ __device__ inline void ws_locate(const WsTable& tab, long long B, int* j_out, int* t_out) {
@@ -1223,6 +1280,10 @@ wgq_stream_kernel(const WsTable tab, const float* __restrict__ zeros) {
         case V_ + 9:                                                                                                \
             wq_segment_call<CLS_, LTW_, false>(jb.a, jb.b, zeros, jb.CA, jb.CB, jb.ca0, jb.cb0, jb.Hb, jb.Wb,      \
                                                jb.tiles_h, jb.tiles_w, t0, t1, slab);                               \
+            break;                                                                                                  \
+        case 256 + V_:                                                                                              \
+            wq_segment_call<CLS_, LTW_, true, true>(jb.a, jb.b, zeros, jb.CA, jb.CB, jb.ca0, jb.cb0, jb.Hb, jb.Wb, \
+                                                    jb.tiles_h, jb.tiles_w, t0, t1, slab);                          \
             break;
 #define GX_WR_CASE(V_, CLS_, W_)                                                                                    \
         case V_:                                                                                                    \
@@ -1232,6 +1293,11 @@ wgq_stream_kernel(const WsTable tab, const float* __restrict__ zeros) {
 #define GX_WF_CASE(V_, CLS_, W_)                                                                                    \
         case 128 + V_:                                                                                              \
             wr_segment_call<CLS_, 100000 + W_>(jb.a, jb.b, zeros, jb.N, jb.CA, jb.CB, jb.ca0, jb.cb0, jb.Hb, t0, t1, slab, jb.amax2); \
+            break;
+        // ... and on ONE bf16 piece per operand (variant + 256: gx_wgq_precision(3); the LDS-DMA tiles 0 .. 8 likewise, GX_WS_CASE)
+#define GX_W1_CASE(V_, CLS_, W_)                                                                                    \
+        case 256 + V_:                                                                                              \
+            wr_segment_call<CLS_, 200000 + W_>(jb.a, jb.b, zeros, jb.N, jb.CA, jb.CB, jb.ca0, jb.cb0, jb.Hb, t0, t1, slab); \
             break;
         switch (jb.variant) {
             GX_WS_CASE(0, WQ_C3, 5) GX_WS_CASE(1, WQ_C3, 4) GX_WS_CASE(2, WQ_C3, 3)
@@ -1259,11 +1325,22 @@ wgq_stream_kernel(const WsTable tab, const float* __restrict__ zeros) {
             GX_WF_CASE(64 + 18, WQ_C3, 2064) GX_WF_CASE(64 + 19, WQ_C3, 2032) GX_WF_CASE(64 + 20, WQ_DR0, 2032)
             GX_WF_CASE(64 + 22, WQ_C5A, 2064) GX_WF_CASE(64 + 23, WQ_C5A, 2032) GX_WF_CASE(64 + 24, WQ_C5B, 2064) GX_WF_CASE(64 + 25, WQ_C5B, 2032)
             GX_WF_CASE(96 + 18, WQ_C3, 3064)
+            GX_W1_CASE(18, WQ_C3, 64) GX_W1_CASE(19, WQ_C3, 32) GX_W1_CASE(20, WQ_DR0, 32) GX_W1_CASE(21, WQ_DR1, 32)
+            GX_W1_CASE(22, WQ_C5A, 64) GX_W1_CASE(23, WQ_C5A, 32) GX_W1_CASE(24, WQ_C5B, 64) GX_W1_CASE(25, WQ_C5B, 32)
+            GX_W1_CASE(26, WQ_C3, 16) GX_W1_CASE(27, WQ_DR0, 16) GX_W1_CASE(28, WQ_DR1, 16)
+            GX_W1_CASE(29, WQ_C3, 128) GX_W1_CASE(30, WQ_DR0, 64) GX_W1_CASE(31, WQ_DR1, 64)
+            GX_W1_CASE(32, WQ_C5A, 16) GX_W1_CASE(33, WQ_C5B, 16)
+            GX_W1_CASE(32 + 18, WQ_C3, 1064) GX_W1_CASE(32 + 19, WQ_C3, 1032) GX_W1_CASE(32 + 20, WQ_DR0, 1032) GX_W1_CASE(32 + 21, WQ_DR1, 1032)
+            GX_W1_CASE(32 + 22, WQ_C5A, 1064) GX_W1_CASE(32 + 23, WQ_C5A, 1032) GX_W1_CASE(32 + 24, WQ_C5B, 1064) GX_W1_CASE(32 + 25, WQ_C5B, 1032)
+            GX_W1_CASE(64 + 18, WQ_C3, 2064) GX_W1_CASE(64 + 19, WQ_C3, 2032) GX_W1_CASE(64 + 20, WQ_DR0, 2032) GX_W1_CASE(64 + 21, WQ_DR1, 2032)
+            GX_W1_CASE(64 + 22, WQ_C5A, 2064) GX_W1_CASE(64 + 23, WQ_C5A, 2032) GX_W1_CASE(64 + 24, WQ_C5B, 2064) GX_W1_CASE(64 + 25, WQ_C5B, 2032)
+            GX_W1_CASE(96 + 18, WQ_C3, 3064)
             default: break;
         }
 #undef GX_WS_CASE
 #undef GX_WR_CASE
 #undef GX_WF_CASE
+#undef GX_W1_CASE
         __syncthreads();          // the next segment's first DMA re-uses stage 0
     }
     if (tab.times && threadIdx.x == 0) {          // measurement: when did this workgroup start and finish
@@ -1332,10 +1409,17 @@ double g_wgq_flops_f16 = 0.0, g_wgq_flops_all = 0.0;      // of the last stream-
 int g_wgq_f16 = -1;
 bool wgq_f16() {
     if (g_wgq_f16 < 0) {
+        const int lv = gx_env_matmul_level();          // GENESIS_MATMUL_PRECISION decides ahead of the per-family variables
         const char* env = getenv("GENESIS_WGQ_F16X3");
-        g_wgq_f16 = (env && env[0] == '0') ? 0 : 1;
+        g_wgq_f16 = lv >= 0 ? (lv == 1 ? 1 : 0) : ((env && env[0] == '0') ? 0 : 1);
     }
     return g_wgq_f16 != 0;
+}
+// one bf16 piece per operand everywhere on the bf16 pipe (gx_wgq_precision(3), GENESIS_MATMUL_PRECISION=medium): variants + 256
+int g_wgq_b1 = -1;
+bool wgq_b1() {
+    if (g_wgq_b1 < 0) g_wgq_b1 = gx_env_matmul_level() == 2 ? 1 : 0;
+    return g_wgq_b1 != 0;
 }
 // units per fp16-piece tile by row-ring variant 18 .. 28 (0: the variant has no fp16 form), re-fitted with GENESIS_WGQ_TIMES on the
 // metric step next to the bf16 / LDS-DMA variants of the same launch: 64 - 78 % of the bf16 tile (the 10-tap row parity gains
@@ -1367,29 +1451,31 @@ bool ws_f16_variant(int rv) { return rv >= 18 && rv <= 33; }
 int g_wgq_b6 = -1;
 bool wgq_b6() {
     if (g_wgq_b6 < 0) {
+        const int lv = gx_env_matmul_level();
         const char* env = getenv("GENESIS_WGQ_BF16X6");
-        g_wgq_b6 = (env && env[0] == '0') ? 0 : 1;
+        g_wgq_b6 = lv >= 0 ? (lv > 0 ? 1 : 0) : ((env && env[0] == '0') ? 0 : 1);
     }
     return g_wgq_b6 != 0;
 }
 
-template <int CLS, int LTW, bool B6>
+template <int CLS, int LTW, bool B6, bool B1 = false>
 void wgq_launch_inst(const WqTable& tab, int total_wgs, const float* zeros, hipStream_t s) {
     using WT = WqTap<CLS>;
     constexpr int TW = 1 << LTW, TH = 64 >> LTW;
     constexpr size_t lds = (size_t)2 * (64 * (TH * WT::SA * TW / 4) + 64 * kSB) * 16;
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgq_kernel<CLS, LTW, B6>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgq_kernel<CLS, LTW, B6, B1>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr = true;
     }
-    hipLaunchKernelGGL((wgq_kernel<CLS, LTW, B6>), dim3(total_wgs), dim3(256), lds, s, tab, zeros);
+    hipLaunchKernelGGL((wgq_kernel<CLS, LTW, B6, B1>), dim3(total_wgs), dim3(256), lds, s, tab, zeros);
 }
 
 template <int CLS, int LTW>
 void wgq_launch_pipe(const WqTable& tab, int total_wgs, const float* zeros, hipStream_t s) {
-    if (wgq_b6()) wgq_launch_inst<CLS, LTW, true>(tab, total_wgs, zeros, s);
+    if (wgq_b6() && wgq_b1()) wgq_launch_inst<CLS, LTW, true, true>(tab, total_wgs, zeros, s);
+    else if (wgq_b6()) wgq_launch_inst<CLS, LTW, true>(tab, total_wgs, zeros, s);
     else wgq_launch_inst<CLS, LTW, false>(tab, total_wgs, zeros, s);
 }
 
@@ -1520,6 +1606,17 @@ void ws_cost_init() {
     if (sscanf(env, "%d,%d,%d,%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8) == 9)
         for (int i = 0; i < 9; ++i) if (v[i] > 0) g_ws_cost[(wgq_b6() ? 0 : 9) + i] = v[i];
 }
+// units per one-piece tile: a FIRST FIT, not a measurement -- per variant, the line through the measured costs of its six-product
+// (g_ws_cost) and three-product (g_ws_cost_f16) tiles, cost = a + b * products, taken at one product, and never below a quarter of
+// the six-product tile (the staging / prologue share the line leaves); the LDS-DMA tiles (0 .. 8, no fp16 form): half their cost.
+// GENESIS_WGQ_TIMES on a mode-3 step shows how well it balances.
+int ws_b1cost(int v) {
+    const int b6 = g_ws_cost[v];
+    if (v < 18 || v > 33) return b6 / 2;
+    const int f3 = ws_f16cost(v);
+    const int c = f3 - 2 * (b6 - f3) / 3;
+    return c > b6 / 4 ? c : b6 / 4;
+}
 
 // row-ring tiles (wr_segment): on the bf16 pipe, for full-width rows of 32 / 64 pixels; GENESIS_WGQ_RING=0 / gx_wgq_ring(0)
 // keep every layer on the 64-pixel LDS-DMA tiles (the A/B reference)
@@ -1637,6 +1734,12 @@ int wgq_launch_stream(std::vector<PendingJob*>& jobs, hipStream_t s, std::vector
                     jb.w_first = 0; jb.N = q.job.N;
                     jb.amax2 = nullptr;
                     // (the k-split 10-tap row parity at 32 pixels has no fp16 form: its split pieces do not fit the tile's free slots)
+                    if (wgq_b1() && wgq_b6()) {
+                        // one bf16 piece per operand: the row-ring tile (and its k-split forms: their cost scaled like the
+                        // six-product one's) or the LDS-DMA tile (0 .. 8); the operands' maxima (q.am_out) are not read
+                        jb.cost = rv >= 0 ? (int)((long long)jb.cost * ws_b1cost(rv) / g_ws_cost[rv]) : ws_b1cost(jb.variant);
+                        jb.variant += 256;
+                    } else
                     if (rv >= 0 && ws_f16_variant(rv) && !(jb.variant != rv && (rv == 21 || rv > 25)) && q.am_out && wgq_f16() && nfin < 2 * kMaxFin - 2) {
                         // both operands' maxima are known: two fp16 pieces per value, three piece products (k-split forms: the fp16
                         // tile's cost scaled like the bf16 one's)
@@ -1653,7 +1756,7 @@ int wgq_launch_stream(std::vector<PendingJob*>& jobs, hipStream_t s, std::vector
                         }
                     }
                     tab.U += (long long)jb.ntiles * jb.cost;
-                    if (jb.variant >= 128) flops_f16 += q.flops / nblk;
+                    if (jb.variant >= 128 && jb.variant < 256) flops_f16 += q.flops / nblk;
                     slots.push_back(WsSlot{&q, blk, 0});
                 }
                 flops += q.flops;
@@ -1925,14 +2028,16 @@ int gx_wgq_flush(hipStream_t s) {
 }
 
 extern "C" int gx_wgq_precision(int mode) {
-    GX_CHECK_ARG(mode >= -1 && mode <= 2, "gx_wgq_precision: mode must be 0 (fp32 matrix pipe), 1 (bf16 pipe, fp32 products from six "
+    GX_CHECK_ARG(mode >= -1 && mode <= 3, "gx_wgq_precision: mode must be 0 (fp32 matrix pipe), 1 (bf16 pipe, fp32 products from six "
                                           "bf16 piece products), 2 (as 1, three fp16 piece products where both operands' maxima are "
-                                          "known) or -1 (the environment's default)");
-    if (mode < 0) { g_wgq_b6 = -1; g_wgq_f16 = -1; return GX_OK; }
+                                          "known), 3 (as 1, one bf16 piece per operand) or -1 (the environment's default)");
+    if (mode < 0) { g_wgq_b6 = -1; g_wgq_f16 = -1; g_wgq_b1 = -1; return GX_OK; }
     g_wgq_b6 = mode ? 1 : 0;
     g_wgq_f16 = mode == 2 ? 1 : 0;
+    g_wgq_b1 = mode == 3 ? 1 : 0;
     return GX_OK;
 }
+int gx_wgq_mode_now(void) { return !wgq_b6() ? 0 : (wgq_b1() ? 3 : (wgq_f16() ? 2 : 1)); }
 
 extern "C" double gx_wgq_last_f16_share(void) { return g_wgq_flops_all > 0.0 ? g_wgq_flops_f16 / g_wgq_flops_all : 0.0; }
 

@@ -422,7 +422,10 @@ __device__ __forceinline__ void wino_split8_f16(const float (&v)[8], float sc, w
 //           MFMAs -- the path is saturated exactly when the matrix pipe would be (measured: 48.9 us, 39.3 us without the A
 //           loads).  Twice the tiles per A operand halve that traffic per MFMA, and the register budget pays for an A
 //           prefetch three positions deep instead of one.
-template <int NB, bool F16 = false> struct WHCfg {
+// PF: the piece form -- 0 three bf16 pieces (six piece products), 1 two fp16 pieces (three), 2 ONE bf16 piece (one product: U packed as
+// one bf16 plane, kinds 65 / 66; V rounded to bf16 in registers; both round to nearest even)
+enum { WPF_B6 = 0, WPF_F3 = 1, WPF_B1 = 2 };
+template <int NB, int PF = WPF_B6> struct WHCfg {
     static constexpr int TROWS = 4 * NB;                  // Winograd tile rows per workgroup (8 columns)
     static constexpr int PRH = 2 * TROWS + 2;             // raw patch rows (10 / 18), 18 columns as [parity 2][PLANE 10]
     static constexpr int USED = PRH * 20;                 // floats per channel (200 / 360)
@@ -434,18 +437,21 @@ template <int NB, bool F16 = false> struct WHCfg {
     static constexpr int NSETS = NB == 1 ? 2 : 4;         // A register sets (position nu of a chunk uses set nu % NSETS)
     static constexpr int LOOK = NB == 1 ? 1 : 2;          // ... loaded LOOK positions ahead (three sets live at NB = 2: 72 registers)
     static constexpr size_t LDS_BYTES = 2 * RAW_FLOATS * 4 > 32768 ? 2 * RAW_FLOATS * 4 : 32768;    // (the epilogue's exchange buffer: 32 KB)
+    static constexpr int NP = PF == WPF_B1 ? 1 : (PF == WPF_F3 ? 2 : 3);     // A pieces loaded per value
+    static constexpr int POSB = (PF == WPF_B1 ? 1 : 3) * 2048;                // bytes of one position's A operands (fp16: slot 2 unused)
 };
 
 // F16: the operands as TWO fp16 pieces (U * 2^eU packed that way: kinds 45 / 46; V * 2^eV split in registers), three piece products
 // per fp32 product instead of six -- half the MFMAs, two thirds of the A-operand traffic, a 24-VALU split per octet instead of 44.
 // eU from the weight tensor's largest magnitude (the packing's trailer; |U| <= 2.25 max |g|), eV from the INPUT tensor's, handed
 // over by the kernel that wrote it (g.xam*; |V| <= 4 max |d|); the outputs are scaled back by 2^-(eU + eV).
-template <int NB, bool F16>
+template <int NB, int PF>
 __global__ void __launch_bounds__(256, NB == 1 ? 2 : 1)
 wino_conv_h_kernel(const float* __restrict__ in, const float* __restrict__ in2, const unsigned* __restrict__ U,
                    float* __restrict__ out, float* __restrict__ out2, const WinoGeom g) {
-    using C = WHCfg<NB, F16>;
-    constexpr int NP = F16 ? 2 : 3;
+    using C = WHCfg<NB, PF>;
+    constexpr bool F16 = PF == WPF_F3, B1 = PF == WPF_B1;
+    constexpr int NP = C::NP, POSB = C::POSB;
     constexpr int PITCH = C::PITCH, NSETS = C::NSETS, LOOK = C::LOOK;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* raw = lds;                       // [2][HKC][PITCH]
@@ -511,9 +517,9 @@ wino_conv_h_kernel(const float* __restrict__ in, const float* __restrict__ in2, 
     }
 
     // ---- A operands: [m tile][chunk][position][piece][m half][lane][16 B]
-    const char* Uw = reinterpret_cast<const char*>(U) + ((size_t)my * nchunks * 16 + 4 * wave) * 6144 + lane * 16;
+    const char* Uw = reinterpret_cast<const char*>(U) + ((size_t)my * nchunks * 16 + 4 * wave) * POSB + lane * 16;
     auto load_a = [&](w_bf16x8 (&a)[2][3], int c, int nu) {
-        const char* p = Uw + ((size_t)c * 16 + nu) * 6144;
+        const char* p = Uw + ((size_t)c * 16 + nu) * POSB;
 #pragma unroll
         for (int pc = 0; pc < NP; ++pc)
 #pragma unroll
@@ -593,6 +599,10 @@ wino_conv_h_kernel(const float* __restrict__ in, const float* __restrict__ in2, 
                     v[ch] = nu == 0 ? t[nb][ch][0] - t[nb][ch][2]
                                     : (nu == 1 ? t[nb][ch][1] + t[nb][ch][2] : (nu == 2 ? t[nb][ch][2] - t[nb][ch][1] : t[nb][ch][1] - t[nb][ch][3]));
                 if (GX_WH_ABL & 4) { b[nb][0] = acur[0][0]; b[nb][1] = acur[0][1]; b[nb][2] = acur[0][2]; }
+                else if constexpr (B1) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) b[nb][0][e] = (__bf16)v[e];
+                }
                 else if constexpr (F16) wino_split8_f16(v, scV, b[nb][0], b[nb][1]);
                 else wino_split8(v, b[nb][0], b[nb][1], b[nb][2]);
             }
@@ -602,6 +612,10 @@ wino_conv_h_kernel(const float* __restrict__ in, const float* __restrict__ in2, 
                 for (int nb = 0; nb < NB; ++nb) {
                     w_f32x16 cc = acc[nu][mi][nb];        // pieces: 0 hi, 1 mid, 2 lo; small terms first
                     if (GX_WH_ABL & 1) { cc[0] += (float)acur[mi][0][0] * (float)b[nb][0][0] + (float)acur[mi][1][1] * (float)b[nb][1][1] + (float)acur[mi][2][2] * (float)b[nb][2][2]; acc[nu][mi][nb] = cc; continue; }
+                    if constexpr (B1) {
+                        acc[nu][mi][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acur[mi][0], b[nb][0], cc, 0, 0, 0);
+                        continue;
+                    }
                     if constexpr (F16) {      // pieces: 0 hi, 1 lo; small terms first
                         cc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(w_f16x8, acur[mi][1]), __builtin_bit_cast(w_f16x8, b[nb][0]), cc, 0, 0, 0);
                         cc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(w_f16x8, acur[mi][0]), __builtin_bit_cast(w_f16x8, b[nb][1]), cc, 0, 0, 0);
@@ -674,10 +688,16 @@ wino_conv_h_kernel(const float* __restrict__ in, const float* __restrict__ in2, 
 }
 
 // U for the bf16 pipe: the thread of an even k writes the three words (k, k + 1) of position p
+// (b1: ONE bf16 piece, rounded to nearest even, in the one-piece layout -- gx_wino_h_word with NP = 1)
 __device__ __forceinline__ void wino_h_store(unsigned* __restrict__ U, float v0, float v1, int m, int k, int p, int Kpad16,
-                                             bool f16 = false, int f16_exp = 0) {
+                                             bool f16 = false, int f16_exp = 0, bool b1 = false) {
     unsigned short pc[2][3];
     const float v[2] = {v0, v1};
+    if (b1) {
+        U[gx_wino_h_word(m, k, p, 0, Kpad16, 1)] = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)v0) |
+                                                   ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)v1) << 16);
+        return;
+    }
     if (f16) {          // two fp16 pieces of v * 2^f16_exp (piece slot 2 stays unused)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -704,15 +724,15 @@ __device__ __forceinline__ void wino_h_store(unsigned* __restrict__ U, float v0,
     for (int q = 0; q < 3; ++q) U[gx_wino_h_word(m, k, p, q, Kpad16)] = (unsigned)pc[0][q] | ((unsigned)pc[1][q] << 16);
 }
 
-// amax: non-NULL = the fp16-piece form (two pieces of U * 2^e, e from the weights' largest magnitude *amax)
+// amax: non-NULL = the fp16-piece form (two pieces of U * 2^e, e from the weights' largest magnitude *amax); b1: one bf16 piece
 __global__ void wino_pack_h_kernel(const float* __restrict__ w, unsigned* __restrict__ U, int mode, int Co, int Ci, int Kpad16,
-                                   int Mpad, const float* __restrict__ amax) {
+                                   int Mpad, const float* __restrict__ amax, int b1) {
     const int total = 16 * (Kpad16 / 2) * Mpad;
     const int f16_exp = amax ? gx_f16_scale_exp(2.25f * *amax) : 0;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int m = idx % Mpad, k = 2 * ((idx / Mpad) % (Kpad16 / 2)), p = idx / (Mpad * (Kpad16 / 2));
         wino_h_store(U, gx_wino_u_value(w, mode, Co, Ci, m, k, p), gx_wino_u_value(w, mode, Co, Ci, m, k + 1, p), m, k, p, Kpad16,
-                     amax != nullptr, f16_exp);
+                     amax != nullptr, f16_exp, b1 != 0);
     }
 }
 
@@ -726,7 +746,7 @@ wino_pair_amax_kernel(const float* __restrict__ w1, const float* __restrict__ w2
 }
 __global__ void wino_pack_pair_h_kernel(const float* __restrict__ w1, const float* __restrict__ w2, unsigned* __restrict__ Uf,
                                         unsigned* __restrict__ Ud, int Co1, int Co2, int Ci, int KpadF, int MpadF, int KpadD,
-                                        int MpadD, int f16) {
+                                        int MpadD, int f16, int b1) {
     const int totF = 16 * (KpadF / 2) * MpadF, totD = 16 * (KpadD / 2) * MpadD;
     int f16_exp = 0;
     if (f16) {
@@ -743,7 +763,7 @@ __global__ void wino_pack_pair_h_kernel(const float* __restrict__ w1, const floa
 #pragma unroll
             for (int e = 0; e < 2; ++e)
                 v[e] = m < Co1 ? gx_wino_u_value(w1, 0, Co1, Ci, m, k + e, p) : gx_wino_u_value(w2, 0, Co2, Ci, m - Co1, k + e, p);
-            wino_h_store(Uf, v[0], v[1], m, k, p, KpadF, f16 != 0, f16_exp);
+            wino_h_store(Uf, v[0], v[1], m, k, p, KpadF, f16 != 0, f16_exp, b1 != 0);
         } else {
             const int i = idx - totF;
             const int m = i % MpadD, k = 2 * ((i / MpadD) % (KpadD / 2)), p = i / (MpadD * (KpadD / 2));
@@ -751,7 +771,7 @@ __global__ void wino_pack_pair_h_kernel(const float* __restrict__ w1, const floa
 #pragma unroll
             for (int e = 0; e < 2; ++e)
                 v[e] = k + e < Co1 ? gx_wino_u_value(w1, 1, Co1, Ci, m, k + e, p) : gx_wino_u_value(w2, 1, Co2, Ci, m, k + e - Co1, p);
-            wino_h_store(Ud, v[0], v[1], m, k, p, KpadD, f16 != 0, f16_exp);
+            wino_h_store(Ud, v[0], v[1], m, k, p, KpadD, f16 != 0, f16_exp, b1 != 0);
         }
     }
 }
@@ -761,10 +781,18 @@ __global__ void wino_pack_pair_h_kernel(const float* __restrict__ w1, const floa
 static int g_wino_h = -1;      // 1 (default): the bf16 pipe; GENESIS_WINO_BF16X6=0 / gx_wino_precision(0): the fp32 pipe
 bool gx_wino_h_on() {
     if (g_wino_h < 0) {
+        const int lv = gx_env_matmul_level();          // GENESIS_MATMUL_PRECISION decides ahead of the per-family variables
         const char* env = getenv("GENESIS_WINO_BF16X6");
-        g_wino_h = (env && env[0] == '0') ? 0 : 1;
+        g_wino_h = lv >= 0 ? (lv > 0 ? 1 : 0) : ((env && env[0] == '0') ? 0 : 1);
     }
     return g_wino_h == 1;
+}
+// the one-piece form (gx_wino_precision(3), GENESIS_MATMUL_PRECISION=medium): one bf16 piece per operand; takes precedence over the
+// fp16-piece form -- an armed gx_conv_input_amax hint is ignored (and still cleared by the launch)
+static int g_wino_b1 = -1;
+bool gx_wino_b1_on(void) {
+    if (g_wino_b1 < 0) g_wino_b1 = gx_env_matmul_level() == 2 ? 1 : 0;
+    return g_wino_b1 == 1 && gx_wino_h_on();
 }
 
 // ---- the fp16-piece form: 2 (default) where the input tensor's partial maxima were handed in (gx_conv_input_amax);
@@ -773,11 +801,13 @@ static double g_wino_flops_f16 = 0.0, g_wino_flops_all = 0.0;      // bf16-pipe 
 static int g_wino_f16 = -1;
 static bool wino_f16_on() {
     if (g_wino_f16 < 0) {
+        const int lv = gx_env_matmul_level();
         const char* env = getenv("GENESIS_WINO_F16X3");
-        g_wino_f16 = (env && env[0] == '0') ? 0 : 1;
+        g_wino_f16 = lv >= 0 ? (lv == 1 ? 1 : 0) : ((env && env[0] == '0') ? 0 : 1);
     }
-    return g_wino_f16 == 1 && gx_wino_h_on();
+    return g_wino_f16 == 1 && gx_wino_h_on() && !gx_wino_b1_on();
 }
+int gx_wino_mode_now(void) { return !gx_wino_h_on() ? 0 : (gx_wino_b1_on() ? 3 : (wino_f16_on() ? 2 : 1)); }
 namespace { struct WinoHint { const float* p0; const float* p1; int n0, n1; }; thread_local WinoHint t_wino_hint = {nullptr, nullptr, 0, 0}; }
 // true: the NEXT Winograd launch of this thread runs on fp16 pieces (the caller packs kinds 45 / 46 for it)
 // (every workgroup of the Winograd kernel reduces the partial maxima itself: worth it up to ~1500 of them -- GroupNorm(8) at any batch
@@ -828,6 +858,7 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
                        int K, int M, int H, int W, hipStream_t s) {
     const bool h = gx_wino_h_on();          // (the operands in U were packed for the same pipe: wino_kpad / the pack kinds)
     const bool f16 = gx_wino_f16_pending(); // (... and, with the input's maxima handed in, as fp16 pieces: the caller asked the same question)
+    const bool b1 = gx_wino_b1_on();        // (... or as one bf16 piece: packs 65 / 66)
     WinoGeom g;
     g.xam0 = f16 ? t_wino_hint.p0 : nullptr; g.xn0 = f16 ? t_wino_hint.n0 : 0;
     g.xam1 = f16 ? t_wino_hint.p1 : nullptr; g.xn1 = f16 ? t_wino_hint.n1 : 0;
@@ -844,7 +875,7 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
     // (128 -> 64): one wave per SIMD has nobody to hand the matrix pipe to while it waits -- and is kept behind
     // GENESIS_WINO_NB=2 for measurement only.
     static const char* nb_env = getenv("GENESIS_WINO_NB");
-    const int nb = (h && !f16 && (H % 16) == 0 && nb_env && nb_env[0] == '2') ? 2 : 1;
+    const int nb = (h && !f16 && !b1 && (H % 16) == 0 && nb_env && nb_env[0] == '2') ? 2 : 1;
     g.tiles_h = H / (2 * WTH * nb);
     g.tiles_w = W / (2 * WTW);
     static bool attr_set = false;
@@ -853,11 +884,13 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<1, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<1, WPF_B6>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<1, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<1, WPF_F3>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<2, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<1, WPF_B1>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<2, WPF_B6>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
@@ -867,13 +900,16 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
         const double bytes = 4.0 * ((double)N * K * H * W + (double)N * M * H * W + 9.0 * K * M);
         GxProf pf(KID_WINO, s, flops, bytes);
         if (h && nb == 2)
-            hipLaunchKernelGGL((wino_conv_h_kernel<2, false>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+            hipLaunchKernelGGL((wino_conv_h_kernel<2, WPF_B6>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+                               reinterpret_cast<const unsigned*>(U), out, out2, g);
+        else if (h && b1)
+            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B1>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else if (h && f16)
-            hipLaunchKernelGGL((wino_conv_h_kernel<1, true>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_F3>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else if (h)
-            hipLaunchKernelGGL((wino_conv_h_kernel<1, false>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B6>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else
         hipLaunchKernelGGL(wino_conv_kernel, dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2, U,
@@ -906,11 +942,13 @@ static size_t wino_u_bytes(int K, int M) {
 }
 
 int gx_wino_precision(int mode) {
-    GX_CHECK_ARG(mode >= -1 && mode <= 2, "gx_wino_precision: mode must be 0 (fp32 matrix pipe), 1 (bf16 pipe, six piece products), 2 (as 1, "
-                                          "three fp16 piece products where the input's maxima are handed in) or -1 (the environment's default)");
-    if (mode < 0) { g_wino_h = -1; g_wino_f16 = -1; return GX_OK; }
+    GX_CHECK_ARG(mode >= -1 && mode <= 3, "gx_wino_precision: mode must be 0 (fp32 matrix pipe), 1 (bf16 pipe, six piece products), 2 (as 1, "
+                                          "three fp16 piece products where the input's maxima are handed in), 3 (as 1, one bf16 piece per "
+                                          "operand) or -1 (the environment's default)");
+    if (mode < 0) { g_wino_h = -1; g_wino_f16 = -1; g_wino_b1 = -1; return GX_OK; }
     g_wino_h = mode ? 1 : 0;
     g_wino_f16 = mode == 2 ? 1 : 0;
+    g_wino_b1 = mode == 3 ? 1 : 0;
     return GX_OK;
 }
 
@@ -933,6 +971,7 @@ int gx_conv3x3_wino(const float* x, const float* w, float* y, int N, int Cin, in
     const int K = mode == 0 ? Cin : Cout, M = mode == 0 ? Cout : Cin;
     const bool h = gx_wino_h_on();
     const bool f16 = gx_wino_f16_pending();
+    const bool b1 = gx_wino_b1_on();
     const int Kpad = gx_round_up(K, h ? HKC : WKC), Mpad = gx_round_up(M, 64);
     float* U = (float*)ws;
     float* trailer = reinterpret_cast<float*>(reinterpret_cast<char*>(U) + gx_kq_h_amax_off(Kpad, Mpad, 16));
@@ -945,7 +984,7 @@ int gx_conv3x3_wino(const float* x, const float* w, float* y, int N, int Cin, in
         GxProf pf(KID_PACK_WEIGHTS, s, 0.0, 8.0 * total);
         if (h)
             hipLaunchKernelGGL(wino_pack_h_kernel, dim3(gx_ceil_div(total / 2, 256)), dim3(256), 0, s, w, (unsigned*)U, mode, Cout,
-                               Cin, Kpad, Mpad, f16 ? (const float*)trailer : (const float*)nullptr);
+                               Cin, Kpad, Mpad, f16 ? (const float*)trailer : (const float*)nullptr, b1 ? 1 : 0);
         else
         hipLaunchKernelGGL(wino_pack_kernel, dim3(gx_ceil_div(total, 256)), dim3(256), 0, s, w, U, mode, Cout, Cin, Kpad,
                            Mpad);
@@ -988,7 +1027,7 @@ static int pair_pack(const float* w1, const float* w2, float* Uf, float* Ud, int
     GxProf pf(KID_PACK_WEIGHTS, s, 0.0, 8.0 * total);
     if (h)
         hipLaunchKernelGGL(wino_pack_pair_h_kernel, dim3(gx_ceil_div(total / 2, 256)), dim3(256), 0, s, w1, w2, (unsigned*)Uf,
-                           (unsigned*)Ud, Co1, Co2, Cin, KpF, MpF, KpD, MpD, f16 ? 1 : 0);
+                           (unsigned*)Ud, Co1, Co2, Cin, KpF, MpF, KpD, MpD, f16 ? 1 : 0, gx_wino_b1_on() ? 1 : 0);
     else
         hipLaunchKernelGGL(wino_pack_pair_kernel, dim3(gx_ceil_div(total, 256)), dim3(256), 0, s, w1, w2, Uf, Ud, Co1, Co2, Cin,
                            KpF, MpF, KpD, MpD);

@@ -12,6 +12,7 @@ import torch.distributed as dist
 from . import _lib
 from . import functions as _fn
 from . import hip_ops as _hip
+from . import precision as _precision
 from .dp import FlatBucket
 from .geco import make_geco
 
@@ -102,6 +103,7 @@ class TrainStep(object):
         self._static_x = None
         self._out = None
         self.iters = 0
+        self._level = _precision.level()      # the matmul precision level the weight cache / graphs were built at
         self.sync_from_rank0()
 
     # ------------------------------------------------------------------ flat buffers
@@ -476,6 +478,7 @@ class TrainStep(object):
     def prepare(self, x):
         """Builds everything a first step() would (weight-cache recording, kernel attributes, graph capture) WITHOUT
         advancing the training state: parameters, Adam moments, step counter and GECO state are restored afterwards."""
+        self._follow_level()
         if not self.use_graph or self.graph is not None:
             return
         state = self._train_state()
@@ -506,9 +509,25 @@ class TrainStep(object):
                 self.bucket.all_reduce(self.pg, packed=True)      # the ONE collective of the step
             self.graph2.replay()
 
+    def _follow_level(self):
+        """The matmul precision level changed since the weight cache was recorded / the graphs were captured
+        (genesis_amd.set_matmul_precision): both hold the old level's packings and kernels.  The cache is recorded afresh by
+        the next iteration and the graphs are RE-CAPTURED by the next step() -- never replayed stale."""
+        lv = _precision.level()
+        if lv == self._level:
+            return
+        if self._wcache is not None:
+            _lib.call('gx_weight_cache_destroy', self._wcache)
+            self._wcache = _lib.query('gx_weight_cache_create')
+            self._wcache_ready = False
+        self.graph = self.graph2 = None
+        self._level = lv
+
     def step(self, x, **forward_kwargs):
         """x [B,3,S,S] on the device.  Returns a device tensor [elbo, err, kl, beta_used] (no host sync).
-        forward_kwargs (rand_pixel / eps / seed_idx injection, parity tests) force the eager path."""
+        forward_kwargs (rand_pixel / eps / seed_idx injection, parity tests) force the eager path.  After a change of the
+        matmul precision level the next call re-records the weight cache and, with graph=True, re-captures the step."""
+        self._follow_level()
         if self.use_graph and not forward_kwargs:
             if self.graph is None:
                 self._capture(x)

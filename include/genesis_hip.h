@@ -53,7 +53,7 @@ int gx_conv3x3_wino_supported(int N, int Cin, int Cout, int H, int W);
 /*      which layers gx_conv3x3_fwd / _dgrad send to it: 0 none, 1 those whose grid fills the chip (default; also
  *      GENESIS_WINOGRAD=0/1/2 in the environment), 2 every supported shape. */
 int gx_conv3x3_wino_policy(int mode);
-/*      which matrix pipe the Winograd layers' products run on: 1 (default; GENESIS_WINO_BF16X6=0/1 in the environment) = the
+/*      which matrix pipe the Winograd layers' products run on (3: one bf16 piece per operand, gx_matmul_precision(2)): 1 (default; GENESIS_WINO_BF16X6=0/1 in the environment) = the
  *      bf16 pipe, every fp32 product U * V from six bf16 piece products accumulated in fp32 (hi + mid + lo pieces hold all 24
  *      mantissa bits: fp32 accuracy, tests/test_kernels_gpu.py::test_conv3x3_winograd); 0 = v_mfma_f32_32x32x2_f32.  Packed
  *      operands are laid out for the pipe in force when they were packed: switch between iterations, not inside one. */
@@ -71,7 +71,8 @@ int gx_wgq_policy(int mode);
  *      products of order <= 2, accumulated in fp32 (v_mfma_f32_32x32x16_bf16): the error against fp64 is that of the
  *      fp32 pipe (tools/bf16x6_probe.hip: 4.8e-7 vs 5.8e-7 relative L2; tests/test_kernels_gpu.py compares both pipes
  *      with fp64), at 6 x 32 instead of 8 x 64 matrix-pipe cycles per 16 contraction steps.  0: the fp32 pipe
- *      (v_mfma_f32_32x32x2_f32).  Environment: GENESIS_WGQ_BF16X6=0. */
+ *      (v_mfma_f32_32x32x2_f32).  Environment: GENESIS_WGQ_BF16X6=0.  3: one bf16 piece per operand on the row-ring and LDS-DMA
+ *      tiles of the stream-K launch (gx_matmul_precision(2)); gx_wgq_last_f16_share counts fp16-piece flops only. */
 int gx_wgq_precision(int mode);
 /*      Tile shape of the bf16-pipe weight gradients for layers whose base rows are 32 or 64 pixels wide (conv3x3 at
  *      32 / 64, transposed conv from 32 x 32): 1 (default) row-ring tiles -- a tile is one full-width base row, the x rows
@@ -109,8 +110,30 @@ int gx_wgq_ring(int on);
  *      an fp16 subnormal and bits drop off one by one; below max |x| * 2^-28 the high piece is subnormal too and below 2^-40 the
  *      value is flushed -- i.e. the representation error is max(2^-23 |x|, 2^-40 max |x|): absolute, not relative, accuracy for the
  *      smallest values of a tensor with one extreme outlier (an element 1e9 times the rest: tests/test_kernels_gpu.py
- *      ::test_fp16x3_transposed_conv_scales_follow_the_tensors[one_huge] pins exactly that bound).  Mode 1 has fp32's range. */
+ *      ::test_fp16x3_transposed_conv_scales_follow_the_tensors[one_huge] pins exactly that bound).  Mode 1 has fp32's range.
+ *      3 (the same for gx_wgq_precision(3) and gx_wino_precision(3)): the same layers from ONE bf16 piece per operand -- see
+ *      gx_matmul_precision below. */
 int gx_kq_precision(int mode);
+/*      ONE switch for the three families above (gx_kq.hip, gx_wino.hip, gx_wgq.hip: the layers that multiply on the 16-bit matrix
+ *      pipe), in torch.set_float32_matmul_precision's vocabulary:
+ *        0 highest -- mode 0 of all three: every product on the fp32 pipe (v_mfma_f32_32x32x2_f32);
+ *        1 high    -- mode 2 of all three (the defaults): fp32-equivalent products from three fp16 / six bf16 piece products;
+ *        2 medium  -- mode 3 of all three: every operand of those layers rounded ONCE to bf16 (round to nearest even), one
+ *                     v_mfma_f32_32x32x16_bf16 per k-step, fp32 accumulation, fp32 tensors.  Error statement: each product carries
+ *                     the relative error of one bf16 product -- two roundings of 2^-9 each, about 2^-8 per product -- and fp32's
+ *                     exponent range (no per-tensor scale: the partial-maxima hints of gx_amax_tap / gx_kq_amax_link /
+ *                     gx_conv_input_amax / gx_wgq_operand_amax are not needed and are ignored when present); sums of many such
+ *                     products are accumulated in fp32.  Layers on the fp32 pipe in every mode stay there: the small-level tap
+ *                     convs, gx_igemm, gx_wstrip, the broadcast convs, dense layers, the LSTM.
+ *        -1         -- every family back to its environment default.
+ *      Returns the level in force BEFORE the call, or GX_MATMUL_MIXED when the three families' modes are not one level (set one by
+ *      one, or by the per-family environment variables); negative: error.  gx_matmul_precision_get() returns the current level
+ *      the same way.  Environment: GENESIS_MATMUL_PRECISION=highest|high|medium, when set, decides all three families' defaults
+ *      ahead of GENESIS_KQ_* / GENESIS_WGQ_* / GENESIS_WINO_*; unset, nothing changes.  Packed operands are laid out per mode:
+ *      switch between iterations, not inside one.  Several ranks: every rank must set the same level (not checked). */
+#define GX_MATMUL_MIXED 3
+int gx_matmul_precision(int level);
+int gx_matmul_precision_get(void);
 /*      Mode 2's per-tensor maximum without a second pass over the tensor: gx_kq_amax_link(parts, capacity, numel) arms a one-shot,
  *      per-thread hand-over -- the next producer that supports it (the register-resident GroupNorm + ReLU kernels behind gx_gn_relu_fwd_parts /
  *      gx_gn_relu_bwd_parts and the decoder head's backward behind gx_gn_relu_bwd_proj: models/genesisv2_config.py:90-99) writes one partial maximum of the gradient it stores
