@@ -124,10 +124,11 @@ def arm(model, x=None):
     st.ctx = _lib.current_ctx()
     book = _book(model)
     cache = book['cache']
-    key = (_param_key(model), _precision.level())
+    key = (_param_key(model), _precision.key())
     if cache is not None and cache[2] != key:
         # the parameters moved (a TrainStep re-homed them into its flat bucket, .to(), load of another state) or the matmul
-        # precision changed (the packings are laid out per level): the recorded (weight pointer, layout) pairs are stale -- start over
+        # precision / tap-conv mode changed (the packings are laid out per level and mode): the recorded (weight pointer, layout)
+        # pairs are stale -- start over
         _lib.call('gx_weight_cache_destroy', cache[0])
         cache[0], cache[1], cache[2] = int(_lib.query('gx_weight_cache_create')), False, key
     if cache is None:
@@ -306,8 +307,8 @@ def graph_stats(model):
 
 
 def _graph_key(model, x):
-    # (the matmul precision level: a graph captured at another level holds that level's kernels and packings)
-    return (tuple(x.shape), x.dtype, x.device, _param_key(model), bool(getattr(model, 'klm_loss', False)), _precision.level())
+    # (the matmul precision level and tap-conv mode: a graph captured under others holds their kernels and packings)
+    return (tuple(x.shape), x.dtype, x.device, _param_key(model), bool(getattr(model, 'klm_loss', False)), _precision.key())
 
 
 def _drop_graph(g):
@@ -322,13 +323,13 @@ class _ReplayFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dummy, g):
         ctx.g = g
-        ctx.level = _precision.level()
+        ctx.level = _precision.key()
         ctx.set_materialize_grads(False)
         return tuple(t.detach() for t in g.roots)
 
     @staticmethod
     def backward(ctx, *grads):
-        _precision.check_backward(ctx.level)
+        _precision.check_backward_key(ctx.level)
         _graph_backward(ctx.g, grads)
         return None, None
 

@@ -26,10 +26,15 @@
 //
 // fp32 in / fp32 accumulate: results are an fmaf chain per output (exact fp32), which is
 // what the stated fp32 parity tolerance of the path needs (no bf16/xf32 shortcuts).
+// The one opt-in exception is gx_tapconv_precision(3) (include/genesis_hip.h): the tap-conv kernels then take one bf16 piece per
+// operand -- one v_mfma_f32_32x32x16_bf16 per pair of taps x 8 channels (TapPairs), fp32 accumulation, weights packed as one bf16
+// plane (kinds 70 ..).  The weight-gradient kernels of this file stay on the fp32 pipe in every mode.
 #include "gx_common.h"
 
+#include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <strings.h>
 #include <vector>
 
 #ifndef GX_WG_ABL
@@ -83,6 +88,34 @@ template <> struct TapCfg<M_C5> {
     __host__ __device__ static constexpr int plane(int) { return 0; }
 };
 
+// The one-bf16 form (gx_tapconv_precision(3)) takes the reduction 16 deep per v_mfma_f32_32x32x16_bf16 as TWO taps x 8 channels:
+// lane half h supplies tap t_h's 8 channels.  Both taps of a pair feed one output class; a class with an odd tap count ends in a
+// single (its second half multiplies zeros).  Pairs are consecutive taps of a class, so most pairs share their offsets' difference.
+template <int MODE> struct TapPairs {
+    int t0[TapCfg<MODE>::NT], t1[TapCfg<MODE>::NT];   // t1 = -1: a single
+    int n;
+    __host__ __device__ constexpr TapPairs() : t0(), t1(), n(0) {
+        using TC = TapCfg<MODE>;
+        for (int c = 0; c < TC::NCLS; ++c) {
+            int pend = -1;
+            for (int t = 0; t < TC::NT; ++t) {
+                if (TC::cls(t) != c) continue;
+                if (pend < 0) { pend = t; continue; }
+                t0[n] = pend; t1[n] = t; ++n; pend = -1;
+            }
+            if (pend >= 0) { t0[n] = pend; t1[n] = -1; ++n; }
+        }
+    }
+};
+typedef __bf16 tap_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 tap_bf16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int tap_u32x4 __attribute__((ext_vector_type(4)));
+// two fp32 values -> one 32-bit word of two bf16, each rounded to nearest even (low half = the first)
+__host__ __device__ __forceinline__ unsigned tap_pk_bf16(float a, float b) {
+    const tap_bf16x2 p = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(unsigned, p);
+}
+
 struct ConvGeom {
     int N;            // images
     int K;            // reduction channels (actual)
@@ -112,7 +145,7 @@ __device__ __forceinline__ float gx_act(float v, int act) {
 // NPOS = halo-tile positions staged per thread per channel (tile <= NPOS*256 floats per channel).
 // MW = waves along M: 1 -> the 4 waves tile 256 pixels (64 each) and all 64 channels; 2 -> a 128-pixel tile, waves 2 x 2
 // (32 channels x 64 pixels each): twice the workgroups for grids that cannot fill the chip with 256-pixel tiles.
-template <int MODE, int NPOS, bool DMA, int MW = 1, bool STATS = false, bool HH = true>
+template <int MODE, int NPOS, bool DMA, int MW = 1, bool STATS = false, bool HH = true, bool B1 = false>
 __device__ __forceinline__ void tapconv_body(const float* __restrict__ in, const float* __restrict__ wp,
                                              const float* __restrict__ bias, float* __restrict__ out,
                                              const ConvGeom& g, float* lds, const int bx, const int by, const int bz,
@@ -210,6 +243,97 @@ __device__ __forceinline__ void tapconv_body(const float* __restrict__ in, const
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[c][i][j][e] = 0.f;
 
+    if constexpr (B1) {
+    // ---- one bf16 piece per operand: 8-channel chunks, LDS stage = input [CHS][8 ch] + weights [NT][64 m][8 ch], all bf16 (16 bytes
+    // per halo position / per (tap, channel)).  The input is converted once, between the register prefetch and its ds_write (so this
+    // form stages through registers whatever the DMA choice); the weights arrive packed (kinds 70 ..: [t][k / 8][m][8 ch] bf16).
+    constexpr int NWB = (NT * 64 + 255) / 256;        // 16-byte weight vectors per thread per chunk
+    constexpr TapPairs<MODE> TP{};
+    const int BUFB = 16 * (CHS + 64 * NT);            // bytes per pipeline stage
+    char* const ldsb = reinterpret_cast<char*>(lds);
+    const int half = lane >> 5;
+    const int a_lane = 16 * CHS + ((lane & 31) + wm * 32) * 16;
+    int bq_off[2];
+#pragma unroll
+    for (int nj = 0; nj < 2; ++nj) {
+        const int p = wn * 64 + nj * 32 + (lane & 31);
+        const int c = p & (TW - 1);
+        const int r = (p >> g.lTW) & (TH - 1);
+        const int gi = p >> (g.lTW + g.lTH);
+        bq_off[nj] = ((gi * (TH + 2 * HL) + r) * HS + c) * 16;
+    }
+    float xin[8][NPOS];
+    tap_u32x4 wreg[NWB];
+    const int nchunks = g.Kpad / 8;
+    const int c_begin = bz * g.chunks_per_split;
+    int c_end = c_begin + g.chunks_per_split;
+    if (c_end > nchunks) c_end = nchunks;
+    const tap_u32x4* wpv = reinterpret_cast<const tap_u32x4*>(wp);
+    const int kq8 = g.Kpad / 8;
+#define GX_TAPB_PREFETCH(chunk)                                                                             \
+    {                                                                                                       \
+        const int ch0_ = (chunk) * 8;                                                                       \
+        _Pragma("unroll") for (int ch = 0; ch < 8; ++ch) {                                                  \
+            const bool chv = (ch0_ + ch) < g.K;                                                             \
+            const int soff_ = (ch0_ + ch) * HiWi * 4;                                                       \
+            _Pragma("unroll") for (int q = 0; q < NPOS; ++q)                                                \
+                xin[ch][q] = chv ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, voff[q], soff_, 0)) : 0.f; \
+        }                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < NWB; ++i) {                                                   \
+            const int v_ = tid + i * 256;                                                                   \
+            if (v_ < NT * 64)                                                                               \
+                wreg[i] = wpv[((size_t)(v_ >> 6) * kq8 + (chunk)) * g.Mpad + m0 + (v_ & 63)];               \
+        }                                                                                                   \
+    }
+#define GX_TAPB_COMMIT(bufb)                                                                                \
+    {                                                                                                       \
+        _Pragma("unroll") for (int q = 0; q < NPOS; ++q) {                                                  \
+            const int pos = tid + q * 256;                                                                  \
+            if (pos < CHS) {                                                                                \
+                tap_u32x4 o_;                                                                               \
+                _Pragma("unroll") for (int i = 0; i < 4; ++i) o_[i] = tap_pk_bf16(xin[2 * i][q], xin[2 * i + 1][q]); \
+                *reinterpret_cast<tap_u32x4*>((bufb) + pos * 16) = o_;                                      \
+            }                                                                                               \
+        }                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < NWB; ++i) {                                                   \
+            const int v_ = tid + i * 256;                                                                   \
+            if (v_ < NT * 64) *reinterpret_cast<tap_u32x4*>((bufb) + 16 * CHS + v_ * 16) = wreg[i];         \
+        }                                                                                                   \
+    }
+    if (c_begin < c_end) GX_TAPB_PREFETCH(c_begin)
+    for (int c = c_begin; c < c_end; ++c) {
+        char* bufb = ldsb + ((c - c_begin) & 1) * BUFB;
+        GX_TAPB_COMMIT(bufb)
+        __syncthreads();
+        if (c + 1 < c_end) GX_TAPB_PREFETCH(c + 1)
+#pragma unroll
+        for (int pi = 0; pi < TP.n; ++pi) {
+            const int t0 = TP.t0[pi], t1 = TP.t1[pi];
+            const bool single = t1 < 0;
+            const int tb = single ? t0 : t1;
+            const int off0 = TC::plane(t0) * PLS + TC::ro(t0) * HS + TC::co(t0);
+            const int offb = TC::plane(tb) * PLS + TC::ro(tb) * HS + TC::co(tb);
+            const int ta = half ? tb : t0, toff = half ? offb : off0;
+            const tap_bf16x8 zero8 = {};
+            const bool dead = single && half;          // the single's second half: zeros, whatever the LDS holds
+            tap_bf16x8 a0 = *reinterpret_cast<const tap_bf16x8*>(bufb + a_lane + ta * 1024);
+            tap_bf16x8 b0 = *reinterpret_cast<const tap_bf16x8*>(bufb + bq_off[0] + toff * 16);
+            tap_bf16x8 b1 = *reinterpret_cast<const tap_bf16x8*>(bufb + bq_off[1] + toff * 16);
+            if (dead) { a0 = zero8; b0 = zero8; b1 = zero8; }
+            const int cl = TC::cls(t0);
+            acc[cl][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[cl][0][0], 0, 0, 0);
+            acc[cl][0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[cl][0][1], 0, 0, 0);
+            if (MI == 2 && hi_half) {
+                tap_bf16x8 a1 = *reinterpret_cast<const tap_bf16x8*>(bufb + a_lane + ta * 1024 + 32 * 16);
+                if (dead) a1 = zero8;
+                acc[cl][MI - 1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[cl][MI - 1][0], 0, 0, 0);
+                acc[cl][MI - 1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[cl][MI - 1][1], 0, 0, 0);
+            }
+        }
+    }
+#undef GX_TAPB_PREFETCH
+#undef GX_TAPB_COMMIT
+    } else {
     // ---- software pipeline over channel chunks ----
     float xin[KC][NPOS];
     f32x4 wreg[NW4];
@@ -316,6 +440,7 @@ __device__ __forceinline__ void tapconv_body(const float* __restrict__ in, const
             }
         }
     }
+    }   // (B1)
 
     // ---- epilogue: C/D layout col = lane&31 (pixel), row = (reg&3)+8*(reg>>2)+4*(lane>>5) (channel) ----
     const size_t out_img_stride = (size_t)g.M * g.Ho * g.Wo;
@@ -461,26 +586,26 @@ __device__ __forceinline__ void tapconv_body(const float* __restrict__ in, const
     }
 }
 
-template <int MODE, int NPOS, bool DMA, int MW = 1, bool HH = true>
+template <int MODE, int NPOS, bool DMA, int MW = 1, bool HH = true, bool B1 = false>
 __global__ void __launch_bounds__(256, 2)
 tapconv_kernel(const float* __restrict__ in, const float* __restrict__ wp,
                const float* __restrict__ bias, float* __restrict__ out, ConvGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    tapconv_body<MODE, NPOS, DMA, MW, false, HH>(in, wp, bias, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y, blockIdx.z, g.par_a);
+    tapconv_body<MODE, NPOS, DMA, MW, false, HH, B1>(in, wp, bias, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y, blockIdx.z, g.par_a);
 }
 
 // Both output-row parities of the transposed conv in one launch: blockIdx.y = 2 * channel_tile + parity.  Twice
 // the workgroups of a single-parity launch, so mid-sized layers fill the chip without splitting the channel
 // reduction (and without the partial-sum traffic and reduce pass that come with it).
-template <int NPOS, bool DMA, int MW = 1, bool STATS = false>
+template <int NPOS, bool DMA, int MW = 1, bool STATS = false, bool B1 = false>
 __global__ void __launch_bounds__(256, 2)
 tapconv_dt_kernel(const float* __restrict__ in, const float* __restrict__ wp0, const float* __restrict__ wp1,
                   const float* __restrict__ bias, float* __restrict__ out, ConvGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (blockIdx.y & 1)
-        tapconv_body<M_DT1, NPOS, DMA, MW, STATS>(in, wp1, bias, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y >> 1, blockIdx.z, 1);
+        tapconv_body<M_DT1, NPOS, DMA, MW, STATS, true, B1>(in, wp1, bias, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y >> 1, blockIdx.z, 1);
     else
-        tapconv_body<M_DT0, NPOS, DMA, MW, STATS>(in, wp0, bias, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y >> 1, blockIdx.z, 0);
+        tapconv_body<M_DT0, NPOS, DMA, MW, STATS, true, B1>(in, wp0, bias, out, g, lds, gx_xcd_tile(blockIdx.x, gridDim.x), blockIdx.y >> 1, blockIdx.z, 0);
 }
 
 // GroupNorm statistics from the per-workgroup block sums the STATS epilogue wrote: stats [N][parts][nblk][2],
@@ -607,6 +732,17 @@ __device__ __forceinline__ void pack_h_store(const float* __restrict__ w, float*
     }
 }
 
+// packs 70 .. 74, 77, 78: 0 .. 4, 7, 8 (the tap-conv kernels' weights) as ONE bf16 piece, w rounded to nearest even, for the
+// one-bf16 form of tapconv_body (gx_tapconv_precision(3)): [t][k / 8][m][8 ch] -- the 8 channels of (t, m) are one 16-byte vector,
+// a lane's A operand.  The thread of an even k writes the word of (k, k + 1), the odd one nothing.  NT * Kpad * Mpad * 2 bytes.
+__device__ __forceinline__ void pack_b1_store(const float* __restrict__ w, float* __restrict__ wp, int pack, int Co, int Ci,
+                                              int m, int k, int t, int Kpad, int Mpad) {
+    if (k & 1) return;
+    pack -= 70;
+    const unsigned wd = tap_pk_bf16(pack_weight_value(w, pack, Co, Ci, m, k, t), pack_weight_value(w, pack, Co, Ci, m, k + 1, t));
+    reinterpret_cast<unsigned*>(wp)[(((size_t)t * (Kpad >> 3) + (k >> 3)) * Mpad + m) * 4 + ((k & 7) >> 1)] = wd;
+}
+
 __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ wp, int pack,
                                     int Co, int Ci, int NT, int Kpad, int Mpad) {
     const int total = NT * Kpad * Mpad;
@@ -615,6 +751,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
         const int m = idx % Mpad;
         const int k = (idx / Mpad) % Kpad;
         const int t = idx / (Mpad * Kpad);
+        if (pack >= 70) { pack_b1_store(w, wp, pack, Co, Ci, m, k, t, Kpad, Mpad); continue; }
         if (pack >= 20) { pack_h_store(w, wp, pack, Co, Ci, m, k, t, NT, Kpad, f16_exp); continue; }
         wp[pack_dest(pack, idx, m, k, t, Kpad, NT)] = pack_weight_value(w, pack, Co, Ci, m, k, t);
     }
@@ -1417,18 +1554,24 @@ struct TapPlan {
     size_t lds_bytes;
     size_t out_elems;  // N*M*Ho*Wo
     dim3 grid;
+    bool b1;           // the one-bf16 form (gx_tapconv_precision(3)): 8-channel chunks, packs 70 ..
 };
 
 template <int MODE>
 int plan_tapconv(int N, int K, int M, int Mpad_pack, int Hb, int Wb, int Hi, int Wi, int Ho, int Wo, int par_a,
-                 TapPlan* pl, const char* name, int ymult = 1, int npix = 256) {
+                 TapPlan* pl, const char* name, int ymult = 1, int npix = 256, bool b1 = false, int max_split = 0) {
     using TC = TapCfg<MODE>;
     ConvGeom& g = pl->g;
+    pl->b1 = b1;
+    const int KC = b1 ? 8 : TC::KC;                 // channels per chunk
     g.N = N; g.K = K; g.M = M;
     g.Kpad = gx_round_up(K, 8); g.Mpad = Mpad_pack;
     g.Hb = Hb; g.Wb = Wb; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.par_a = par_a;
     constexpr int LO_ = (MODE == M_DG) ? 8 : 2;
-    pick_tile(Hb, Wb, npix, TC::PLANES, 2 * LO_ * 256, &g.lTH, &g.lTW, &g.lG, TC::HALO);
+    // (one-bf16 form: the transposed conv's data gradient holds its halo tile to NPOS = 8 -- its register staging is 8 channels x
+    // NPOS floats, and 16 positions per thread spill -- which also keeps its two 16-byte-per-position stages within 116 KiB)
+    const int max_chs = b1 && MODE == M_DG ? LO_ * 256 : 2 * LO_ * 256;
+    pick_tile(Hb, Wb, npix, TC::PLANES, max_chs, &g.lTH, &g.lTW, &g.lG, TC::HALO);
     pl->mw = 256 / npix;
     const int TH = 1 << g.lTH, TW = 1 << g.lTW, G = 1 << g.lG;
     g.tiles_h = gx_ceil_div(Hb, TH); g.tiles_w = gx_ceil_div(Wb, TW);
@@ -1441,11 +1584,11 @@ int plan_tapconv(int N, int K, int M, int Mpad_pack, int Hb, int Wb, int Hi, int
     const int lo = (MODE == M_DG) ? 8 : 2;
     pl->npos = need <= lo ? lo : 2 * lo;
     if (need > 2 * lo) { gx_set_error("%s: halo tile too large (%d floats/channel)", name, CHS); return GX_EINVAL; }
-    pl->lds_bytes = (size_t)2 * (TC::KC * CHS + TC::NT * TC::KC * 64) * sizeof(float);
+    pl->lds_bytes = b1 ? (size_t)2 * 16 * (CHS + TC::NT * 64) : (size_t)2 * (TC::KC * CHS + TC::NT * TC::KC * 64) * sizeof(float);
     if (pl->lds_bytes > 160 * 1024) { gx_set_error("%s: LDS %zu > 160KiB", name, pl->lds_bytes); return GX_EINVAL; }
     const int ptiles = g.tiles_h * g.tiles_w * gx_ceil_div(N, G);
     const int mtiles = gx_ceil_div(M, 64);
-    const int nchunks = g.Kpad / TC::KC;
+    const int nchunks = g.Kpad / KC;
     // split the channel reduction when the (pixel-tile x channel-tile) grid cannot fill 256 CUs x 2
     int nsplit = 1;
     const int base = ptiles * mtiles * ymult;   // ymult: parity classes sharing the launch
@@ -1455,6 +1598,7 @@ int plan_tapconv(int N, int K, int M, int Mpad_pack, int Hb, int Wb, int Hi, int
         if (nsplit > 64) nsplit = 64;
         if (nsplit < 1) nsplit = 1;
     }
+    if (max_split > 0 && nsplit > max_split) nsplit = max_split;
     g.chunks_per_split = gx_ceil_div(nchunks, nsplit);
     nsplit = gx_ceil_div(nchunks, g.chunks_per_split);
     g.nsplit = nsplit;
@@ -1463,25 +1607,25 @@ int plan_tapconv(int N, int K, int M, int Mpad_pack, int Hb, int Wb, int Hi, int
     return GX_OK;
 }
 
-template <int MODE, int NPOS, bool DMA, int MW, bool HH>
+template <int MODE, int NPOS, bool DMA, int MW, bool HH, bool B1>
 void launch_tapconv_inst3(const float* in, const float* wp, const float* bias, float* out, const ConvGeom& g,
                           dim3 grid, size_t lds_bytes, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tapconv_kernel<MODE, NPOS, DMA, MW, HH>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tapconv_kernel<MODE, NPOS, DMA, MW, HH, B1>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL((tapconv_kernel<MODE, NPOS, DMA, MW, HH>), grid, dim3(256), lds_bytes, s, in, wp, bias, out, g);
+    hipLaunchKernelGGL((tapconv_kernel<MODE, NPOS, DMA, MW, HH, B1>), grid, dim3(256), lds_bytes, s, in, wp, bias, out, g);
 }
 // layers of <= 32 output channels (conv3x3 and the stride-1 5x5 conv: MONet / GENESIS, e.g. the data gradients of the gated
 // 32 -> 2 x 32 stacks) skip the upper MFMA tile
-template <int MODE, int NPOS, bool DMA, int MW = 1>
+template <int MODE, int NPOS, bool DMA, int MW = 1, bool B1 = false>
 void launch_tapconv_inst2(const float* in, const float* wp, const float* bias, float* out, const ConvGeom& g,
                           dim3 grid, size_t lds_bytes, hipStream_t s) {
     constexpr bool LOW = MODE == M_C3 || MODE == M_C5;
-    if (LOW && g.M <= 32) launch_tapconv_inst3<MODE, NPOS, DMA, MW, !LOW>(in, wp, bias, out, g, grid, lds_bytes, s);
-    else launch_tapconv_inst3<MODE, NPOS, DMA, MW, true>(in, wp, bias, out, g, grid, lds_bytes, s);
+    if (LOW && g.M <= 32) launch_tapconv_inst3<MODE, NPOS, DMA, MW, !LOW, B1>(in, wp, bias, out, g, grid, lds_bytes, s);
+    else launch_tapconv_inst3<MODE, NPOS, DMA, MW, true, B1>(in, wp, bias, out, g, grid, lds_bytes, s);
 }
 
 const float* zero_page(hipStream_t s);
@@ -1490,6 +1634,14 @@ template <int MODE, int NPOS>
 void launch_tapconv_inst(const float* in, const float* wp, const float* bias, float* out, const TapPlan& pl,
                          hipStream_t s) {
     ConvGeom g = pl.g;
+    if (pl.b1) {          // (the one-bf16 form converts its input in registers: no LDS-DMA staging)
+        g.zeros = nullptr;
+        if constexpr (!(MODE == M_DG && NPOS > 8)) {     // (plan_tapconv: NPOS 8 for the data gradient of the transposed conv)
+            if (pl.mw == 2) launch_tapconv_inst2<MODE, NPOS, false, 2, true>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
+            else launch_tapconv_inst2<MODE, NPOS, false, 1, true>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
+        }
+        return;
+    }
     // LDS-DMA staging measured per mode (B=32, K=7): transposed conv fwd 32->64 481 -> 431 us, its dgrad 462 -> 454,
     // conv3x3 1-2 % slower -> on for the 5x5 modes, off for conv3x3 (GENESIS_TAPCONV_DMA=0/1 forces all modes)
     static const char* dma_env = getenv("GENESIS_TAPCONV_DMA");
@@ -1504,16 +1656,16 @@ void launch_tapconv_inst(const float* in, const float* wp, const float* bias, fl
     else launch_tapconv_inst2<MODE, NPOS, false>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
 }
 
-template <int NPOS, bool DMA, int MW = 1, bool STATS = false>
+template <int NPOS, bool DMA, int MW = 1, bool STATS = false, bool B1 = false>
 void launch_dt(dim3 grid, size_t lds_bytes, hipStream_t s, const float* x, const float* wp0, const float* wp1,
                const float* bias, float* dst, const ConvGeom& g) {
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tapconv_dt_kernel<NPOS, DMA, MW, STATS>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tapconv_dt_kernel<NPOS, DMA, MW, STATS, B1>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL((tapconv_dt_kernel<NPOS, DMA, MW, STATS>), grid, dim3(256), lds_bytes, s, x, wp0, wp1, bias,
+    hipLaunchKernelGGL((tapconv_dt_kernel<NPOS, DMA, MW, STATS, B1>), grid, dim3(256), lds_bytes, s, x, wp0, wp1, bias,
                        dst, g);
 }
 
@@ -1529,6 +1681,7 @@ int launch_tapconv(const float* in, const float* wp, const float* bias, float* d
         const double bytes = 4.0 * ((double)g.N * g.K * g.Hi * g.Wi + (double)g.N * g.M * g.Ho * g.Wo / TC::NCLS +
                                     (double)TC::NT * g.K * g.M);
         GxProf pf(MODE == M_C5 ? KID_DCONV : KID_TAPCONV_C3 + MODE, s, flops, bytes);
+        gx_tapconv_note(pl.b1 ? 3 : 0);
         constexpr int LO = (MODE == M_DG) ? 8 : 2;
         if (pl.npos == LO) launch_tapconv_inst<MODE, LO>(in, wp, bias, dst, pl, s);
         else launch_tapconv_inst<MODE, 2 * LO>(in, wp, bias, dst, pl, s);
@@ -1593,6 +1746,7 @@ __global__ void pack_weights_batch_kernel(const PackEntry* __restrict__ entries,
         const int m = idx % e.Mpad;
         const int k = (idx / e.Mpad) % e.Kpad;
         const int t = idx / (e.Mpad * e.Kpad);
+        if (e.pack >= 70) { pack_b1_store(e.w, e.wp, e.pack, e.Co, e.Ci, m, k, t, e.Kpad, e.Mpad); continue; }
         if (e.pack >= 20) { pack_h_store(e.w, e.wp, e.pack, e.Co, e.Ci, m, k, t, e.NT, e.Kpad, f16_exp); continue; }
         e.wp[pack_dest(e.pack, idx, m, k, t, e.Kpad, e.NT)] = pack_weight_value(e.w, e.pack, e.Co, e.Ci, m, k, t);
     }
@@ -1612,7 +1766,8 @@ int launch_pack(const float* w, float* wp, int pack, int Co, int Ci, int NT, int
         for (const PackEntry& e : c.entries) found = found || (e.w == w && e.pack == pack && e.Co == Co && e.Ci == Ci);
         if (!found) {
             PackEntry e{w, nullptr, pack, Co, Ci, NT, Kpad, Mpad, 0};
-            const size_t pbytes = pack >= 20 ? gx_kq_deconv_h_pack_bytes(Kpad, Mpad, NT) : (size_t)NT * Kpad * Mpad * sizeof(float);
+            const size_t pbytes = pack >= 70 ? (size_t)NT * Kpad * Mpad * 2
+                                              : (pack >= 20 ? gx_kq_deconv_h_pack_bytes(Kpad, Mpad, NT) : (size_t)NT * Kpad * Mpad * sizeof(float));
             if (hipMalloc((void**)&e.wp, pbytes) != hipSuccess) {
                 gx_set_error("weight cache: hipMalloc failed");
                 return GX_ELAUNCH;
@@ -1646,6 +1801,24 @@ int plan_c3(int N, int K, int M, int Mpad, int H, int W, TapPlan* pl, const char
     if (plan_tapconv<M_C3>(N, K, M, Mpad, H, W, H, W, H, W, 0, &p2, name, 1, 128) != GX_OK) return rc;
     *pl = p2;
     return rc;
+}
+
+// the one-bf16 form of a planned layer (gx_tapconv_precision(3)): the same pixel tiles, 8-channel chunks and a channel split no
+// wider than the fp32 plan's, so its partial slabs fit the workspace sized for that plan.  A shape whose halo tile it cannot hold
+// (a transposed conv's data gradient on a 1-pixel grid) keeps the fp32 plan: GX_EINVAL here, and gx_tapconv_last_mode() reports 0.
+template <int MODE>
+int plan_b1(TapPlan* pl, int ymult, const char* name) {
+    const ConvGeom g = pl->g;
+    TapPlan p;
+    int rc = plan_tapconv<MODE>(g.N, g.K, g.M, g.Mpad, g.Hb, g.Wb, g.Hi, g.Wi, g.Ho, g.Wo, g.par_a, &p, name, ymult,
+                                256 / pl->mw, true, g.nsplit);
+    if (rc && pl->mw == 1)        // (a smaller halo tile: 128-pixel tiles)
+        rc = plan_tapconv<MODE>(g.N, g.K, g.M, g.Mpad, g.Hb, g.Wb, g.Hi, g.Wi, g.Ho, g.Wo, g.par_a, &p, name, ymult, 128, true,
+                                g.nsplit);
+    if (rc) return rc;
+    p.g.act = g.act;
+    *pl = p;
+    return GX_OK;
 }
 
 struct WgradPlan {
@@ -2147,6 +2320,27 @@ int gx_wf_flush(hipStream_t s) { return wf_flush(s); }
 int gx_wf_pending(void) { return (int)g_wf.size(); }
 void gx_wf_discard(void) { g_wf.clear(); }
 
+// ---- the tap-conv kernels' and the strips' arithmetic (include/genesis_hip.h: gx_tapconv_precision) ----------------------
+// GENESIS_TAPCONV_PRECISION=default|medium: 0 / 3; unset: 0; an unknown value is reported once and ignored
+static int tap_env_mode() {
+    static const int m = [] {
+        const char* e = getenv("GENESIS_TAPCONV_PRECISION");
+        if (!e || !e[0] || !strcasecmp(e, "default")) return 0;
+        if (!strcasecmp(e, "medium")) return 3;
+        fprintf(stderr, "libgenesis_hip: GENESIS_TAPCONV_PRECISION=%s is not one of default, medium -- ignored\n", e);
+        return 0;
+    }();
+    return m;
+}
+static int g_tap_mode = -1;                 // -1: the environment's default (resolved on first use)
+static thread_local int t_tap_last = -1;    // the mode of this thread's last tap-conv / strip launch
+static int tap_mode_now() {
+    if (g_tap_mode < 0) g_tap_mode = tap_env_mode();
+    return g_tap_mode;
+}
+bool gx_tapconv_b1_on(void) { return tap_mode_now() == 3; }
+void gx_tapconv_note(int mode) { t_tap_last = mode; }
+
 // =================================================================== C ABI
 int gx_defer_flush_wgrad(const GxWgradRed* items, int n, hipStream_t s) {
     // the records of one launch ACCUMULATE into their destinations from different workgroups: two records of one launch
@@ -2195,6 +2389,16 @@ int gx_wgrad_reduce_now(const GxWgradRed& r, hipStream_t s, int accumulate) {
 }
 
 extern "C" {
+
+int gx_tapconv_precision(int mode) {
+    GX_CHECK_ARG(mode == -1 || mode == 0 || mode == 3, "gx_tapconv_precision: mode must be 0 (default: today's arithmetic), "
+                                                       "3 (medium: one bf16 piece per operand) or -1 (the environment's default)");
+    const int prev = tap_mode_now();
+    g_tap_mode = mode < 0 ? tap_env_mode() : mode;
+    return prev;
+}
+int gx_tapconv_precision_get(void) { return tap_mode_now(); }
+int gx_tapconv_last_mode(void) { return t_tap_last; }
 
 // workspace = packed weights (+ split-K partial slabs when the plan splits the reduction)
 static size_t conv3x3_pack_floats(int Cin, int Cout) {
@@ -2405,7 +2609,8 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
-    rc = launch_pack(w, wp, 0, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
+    const bool b1 = gx_tapconv_b1_on() && plan_b1<M_C3>(&pl, 1, "gx_conv3x3_fwd") == GX_OK;
+    rc = launch_pack(w, wp, b1 ? 70 : 0, Cout, Cin, 9, Kpad, Mpad, s, &wpu);       // (70: one bf16 piece)
     if (rc) return rc;
     rc = launch_tapconv<M_C3>(x, wpu, bias, pl.g.nsplit > 1 ? part : y, pl, s, "gx_conv3x3_fwd");
     if (rc) return rc;
@@ -2475,7 +2680,8 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
         if (rc) return rc;
         return gx_wino_launch(dy, wpu, dx, N, Cout, Cin, H, W, s);
     }
-    rc = launch_pack(w, wp, 1, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
+    const bool b1 = gx_tapconv_b1_on() && plan_b1<M_C3>(&pl, 1, "gx_conv3x3_dgrad") == GX_OK;
+    rc = launch_pack(w, wp, b1 ? 71 : 1, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
     if (rc) return rc;
     rc = launch_tapconv<M_C3>(dy, wpu, nullptr, pl.g.nsplit > 1 ? part : dx, pl, s, "gx_conv3x3_dgrad");
     if (rc) return rc;
@@ -2723,7 +2929,8 @@ int gx_conv5x5s1(const float* in, const float* w, float* out, int N, int K, int 
                                 xparts, xn);
     }
     // pack 7: w [M][K]; pack 8: w [K][M] flipped (launch_pack's (Co, Ci) are the weight tensor's leading dimensions)
-    rc = flip ? launch_pack(w, wp, 8, K, M, 25, Kpad, Mpad, s, &wpu) : launch_pack(w, wp, 7, M, K, 25, Kpad, Mpad, s, &wpu);
+    const int b1 = gx_tapconv_b1_on() && plan_b1<M_C5>(&pl, 1, "gx_conv5x5s1") == GX_OK ? 70 : 0;     // packs 77 / 78: one bf16 piece
+    rc = flip ? launch_pack(w, wp, 8 + b1, K, M, 25, Kpad, Mpad, s, &wpu) : launch_pack(w, wp, 7 + b1, M, K, 25, Kpad, Mpad, s, &wpu);
     if (rc) return rc;
     rc = launch_tapconv<M_C5>(in, wpu, nullptr, pl.g.nsplit > 1 ? part : out, pl, s, "gx_conv5x5s1");
     if (rc) return rc;
@@ -2889,10 +3096,6 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
-    rc = launch_pack(w, wp0, 2, Cout, Cin, 15, Kpad, Mpad, s, &wpu0);
-    if (rc) return rc;
-    rc = launch_pack(w, wp1, 3, Cout, Cin, 10, Kpad, Mpad, s, &wpu1);
-    if (rc) return rc;
     // both row parities in one launch (they share the pixel tiling and the channel split, so one reduce
     // finishes the layer)
     TapPlan p0;
@@ -2905,6 +3108,11 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
                                 2, 128) == GX_OK)
             p0 = p2;
     }
+    const int b1 = gx_tapconv_b1_on() && plan_b1<M_DT0>(&p0, 2, "gx_deconv5x5s2_fwd") == GX_OK ? 70 : 0;    // packs 72 / 73
+    rc = launch_pack(w, wp0, 2 + b1, Cout, Cin, 15, Kpad, Mpad, s, &wpu0);
+    if (rc) return rc;
+    rc = launch_pack(w, wp1, 3 + b1, Cout, Cin, 10, Kpad, Mpad, s, &wpu1);
+    if (rc) return rc;
     float* dst = p0.g.nsplit > 1 ? part : y;
     if (stats_parts_out) *stats_parts_out = 0;
     {
@@ -2913,11 +3121,24 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
         const double bytes = 4.0 * ((double)g.N * g.K * g.Hi * g.Wi + (double)g.N * g.M * g.Ho * g.Wo +
                                     25.0 * g.K * g.M);
         GxProf pf(KID_TAPCONV_DT0, s, flops, bytes);
+        gx_tapconv_note(b1 ? 3 : 0);
         dim3 grid(p0.grid.x, p0.grid.y * 2, p0.grid.z);
         ConvGeom gg = p0.g;
         static const char* dma_env = getenv("GENESIS_TAPCONV_DMA");
-        gg.zeros = (dma_env ? dma_env[0] == '1' : true) ? zero_page(s) : nullptr;
-        if (p0.mw == 2) {
+        gg.zeros = (dma_env ? dma_env[0] == '1' : true) && !b1 ? zero_page(s) : nullptr;
+        if (b1) {             // one bf16 piece per operand: register staging (the input is converted on its way into LDS)
+            const bool st_ok = stats && p0.mw == 1 && p0.npos == 2 && gg.nsplit == 1 && gg.lG == 0 && (Cout % 8) == 0;
+            if (st_ok) {
+                gg.stats = stats;
+                gg.stats_parts = gg.tiles_h * gg.tiles_w * 2;
+                if (stats_parts_out) *stats_parts_out = gg.stats_parts;
+                launch_dt<2, false, 1, true, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+            } else if (p0.mw == 2) {
+                if (p0.npos == 2) launch_dt<2, false, 2, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+                else launch_dt<4, false, 2, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+            } else if (p0.npos == 2) launch_dt<2, false, 1, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+            else launch_dt<4, false, 1, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+        } else if (p0.mw == 2) {
             gg.zeros = nullptr;
             if (p0.npos == 2) launch_dt<2, false, 2>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
             else launch_dt<4, false, 2>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
@@ -2977,8 +3198,6 @@ int gx_deconv5x5s2_dgrad(const float* dy, const float* w, float* dx, int N, int 
         if (rc) return rc;
         return gx_kq_deconv_dgrad_launch(dy, wpu, dx, N, Cout, Cin_out, Hin, Win, s);
     }
-    rc = launch_pack(w, wp, 4, Cout, Cin, 25, Kpad, Mpad, s, &wpu);
-    if (rc) return rc;
     TapPlan pl;
     rc = plan_tapconv<M_DG>(N, Cout, Cin_out, Mpad, Hin, Win, 2 * Hin, 2 * Win, Hin, Win, 0, &pl, "gx_deconv5x5s2_dgrad");
     if (rc) return rc;
@@ -2989,6 +3208,9 @@ int gx_deconv5x5s2_dgrad(const float* dy, const float* w, float* dx, int N, int 
                                "gx_deconv5x5s2_dgrad", 1, 128) == GX_OK)
             pl = p2;
     }
+    const bool b1 = gx_tapconv_b1_on() && plan_b1<M_DG>(&pl, 1, "gx_deconv5x5s2_dgrad") == GX_OK;
+    rc = launch_pack(w, wp, b1 ? 74 : 4, Cout, Cin, 25, Kpad, Mpad, s, &wpu);      // (74: one bf16 piece)
+    if (rc) return rc;
     rc = launch_tapconv<M_DG>(dy, wpu, nullptr, pl.g.nsplit > 1 ? part : dx, pl, s, "gx_deconv5x5s2_dgrad");
     if (rc) return rc;
     if (pl.g.nsplit > 1) return launch_splitk_reduce(part, nullptr, dx, pl, s);

@@ -16,6 +16,8 @@
 // up the rest of each line from L2), two waves per SIMD, no barrier until the final reduction.
 // Partial sums: one 9 x 32 x 32 block per workgroup (the four waves added in wave order through LDS), summed over the workgroups
 // in fixed order by two small launches -- bit-reproducible.
+// gx_tapconv_precision(3): wgrad_strip_kernel<true> splits each window row and each dy value into ONE bf16 piece (round to nearest
+// even) and issues one MFMA per tap instead of six; partials and reduce launches as above.
 #include "gx_common.h"
 
 #include <cstdlib>
@@ -58,9 +60,14 @@ __device__ __forceinline__ void ws_split2(float v0, float v1, unsigned& ph, unsi
 // one split row of the window: 10 values (columns 8 j - 1 .. 8 j + 8) as five packed pairs per piece
 struct WsRow { unsigned h[5], m[5], l[5]; };
 
+// (B1, gx_tapconv_precision(3): the high piece alone -- each value rounded once to bf16, to nearest even)
+template <bool B1>
 __device__ __forceinline__ void ws_split_row(const float (&v)[10], WsRow& w) {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) ws_split2(v[2 * i], v[2 * i + 1], w.h[i], w.m[i], w.l[i]);
+    for (int i = 0; i < 5; ++i) {
+        if (B1) w.h[i] = ws_pk(v[2 * i], v[2 * i + 1]);
+        else ws_split2(v[2 * i], v[2 * i + 1], w.h[i], w.m[i], w.l[i]);
+    }
 }
 // the B operand of tap column kw: window elements kw .. kw + 7 (kw = 1: funnel shifts of neighbouring pairs)
 template <int KW>
@@ -87,6 +94,9 @@ struct StripGeom {
 constexpr int kStripC = 32;
 constexpr int kStripPart = 9 * 16 * 64;          // floats of one partial: [tap][accumulator register][lane]
 
+// B1: every window value and every dy value as ONE bf16 piece, one MFMA per tap and row instead of six (gx_tapconv_precision(3));
+// the partials and the fixed-order reduce launches are the same
+template <bool B1>
 __global__ void __launch_bounds__(256, 1)
 wgrad_strip_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ part,
                    float* __restrict__ bias_part, const StripGeom g) {
@@ -146,8 +156,9 @@ wgrad_strip_kernel(const float* __restrict__ x, const float* __restrict__ dy, fl
         {                                                                                             \
             ws_u32x4 ah_, am_, al_;                                                                   \
             _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                           \
-                unsigned h_, m_, l_;                                                                  \
-                ws_split2(rd_[2 * i], rd_[2 * i + 1], h_, m_, l_);                                    \
+                unsigned h_, m_ = 0u, l_ = 0u;                                                        \
+                if (B1) h_ = ws_pk(rd_[2 * i], rd_[2 * i + 1]);                                       \
+                else ws_split2(rd_[2 * i], rd_[2 * i + 1], h_, m_, l_);                               \
                 ah_[i] = h_; am_[i] = m_; al_[i] = l_;                                                \
             }                                                                                         \
             a3_.h = __builtin_bit_cast(ws_bf16x8, ah_); a3_.m = __builtin_bit_cast(ws_bf16x8, am_);   \
@@ -166,9 +177,9 @@ wgrad_strip_kernel(const float* __restrict__ x, const float* __restrict__ dy, fl
         GX_WS_LOAD_X(rx1, y0)
         GX_WS_LOAD_X(rx2, y0 + 1)
         GX_WS_LOAD_D(rd0, y0)
-        ws_split_row(rx0, w0);
-        ws_split_row(rx1, w1);
-        ws_split_row(rx2, w2);
+        ws_split_row<B1>(rx0, w0);
+        ws_split_row<B1>(rx1, w1);
+        ws_split_row<B1>(rx2, w2);
         GX_WS_SPLIT_D(a0, rd0)
         GX_WS_LOAD_X(rx0, y0 + 2)
         GX_WS_LOAD_D(rd0, y0 + 1)
@@ -189,26 +200,29 @@ wgrad_strip_kernel(const float* __restrict__ x, const float* __restrict__ dy, fl
 #define GX_WS_TAPS(kh_, wrow_, a3_)                                                                   \
         {                                                                                             \
             WsB3 bv_[3];                                                                              \
-            bv_[0].h = ws_view<0>(wrow_.h); bv_[0].m = ws_view<0>(wrow_.m); bv_[0].l = ws_view<0>(wrow_.l); \
-            bv_[1].h = ws_view<1>(wrow_.h); bv_[1].m = ws_view<1>(wrow_.m); bv_[1].l = ws_view<1>(wrow_.l); \
-            bv_[2].h = ws_view<2>(wrow_.h); bv_[2].m = ws_view<2>(wrow_.m); bv_[2].l = ws_view<2>(wrow_.l); \
-            GX_WS_PROD(kh_, m, m, a3_)      /* small terms first */                                   \
-            GX_WS_PROD(kh_, l, h, a3_)                                                                \
-            GX_WS_PROD(kh_, h, l, a3_)                                                                \
-            GX_WS_PROD(kh_, m, h, a3_)                                                                \
-            GX_WS_PROD(kh_, h, m, a3_)                                                                \
+            bv_[0].h = ws_view<0>(wrow_.h); bv_[1].h = ws_view<1>(wrow_.h); bv_[2].h = ws_view<2>(wrow_.h); \
+            if (!B1) {                                                                                \
+                bv_[0].m = ws_view<0>(wrow_.m); bv_[0].l = ws_view<0>(wrow_.l);                       \
+                bv_[1].m = ws_view<1>(wrow_.m); bv_[1].l = ws_view<1>(wrow_.l);                       \
+                bv_[2].m = ws_view<2>(wrow_.m); bv_[2].l = ws_view<2>(wrow_.l);                       \
+                GX_WS_PROD(kh_, m, m, a3_)      /* small terms first */                               \
+                GX_WS_PROD(kh_, l, h, a3_)                                                            \
+                GX_WS_PROD(kh_, h, l, a3_)                                                            \
+                GX_WS_PROD(kh_, m, h, a3_)                                                            \
+                GX_WS_PROD(kh_, h, m, a3_)                                                            \
+            }                                                                                         \
             GX_WS_PROD(kh_, h, h, a3_)                                                                \
         }
 #define GX_WS_STEP(wa_, wb_, wc_, wd_, acur_, anxt_, rxc_, rdc_, rxn_, rdn_, r_)                      \
         {                                                                                             \
-            if (!(GX_WS_ABL & 4)) { ws_split_row(rxc_, wd_); GX_WS_SPLIT_D(anxt_, rdc_) }             \
+            if (!(GX_WS_ABL & 4)) { ws_split_row<B1>(rxc_, wd_); GX_WS_SPLIT_D(anxt_, rdc_) }         \
             else { wd_.h[0] ^= __builtin_bit_cast(unsigned, rxc_[0] + rdc_[0]); }                     \
             GX_WS_LOAD_X(rxn_, y0 + (r_) + 5)                                                         \
             GX_WS_LOAD_D(rdn_, y0 + (r_) + 4)                                                         \
             GX_WS_TAPS(0, wa_, acur_)                                                                 \
             GX_WS_TAPS(1, wb_, acur_)                                                                 \
             GX_WS_TAPS(2, wc_, acur_)                                                                 \
-            _Pragma("unroll") for (int i_ = 0; i_ < 54; ++i_) {                                       \
+            _Pragma("unroll") for (int i_ = 0; i_ < (B1 ? 9 : 54); ++i_) {                            \
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      /* one MFMA ... */            \
                 __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);      /* ... three vector-ALU instructions */ \
             }                                                                                         \
@@ -350,7 +364,10 @@ int gx_wstrip_launch(const float* x, const float* dy, float* dw, float* dbias, i
     if (nb * 4 > g.npair) nb = gx_ceil_div(g.npair, 4);
     {
         GxProf pf(KID_WGRAD_C3, s, 2.0 * N * (double)C * C * 9 * H * W, 4.0 * (2.0 * N * C * H * W + (double)nb * kStripPart));
-        hipLaunchKernelGGL(wgrad_strip_kernel, dim3(nb), dim3(256), 0, s, x, dy, part, dbias ? bias_part : (float*)nullptr, g);
+        const bool b1 = gx_tapconv_b1_on();
+        gx_tapconv_note(b1 ? 3 : 0);
+        if (b1) hipLaunchKernelGGL(wgrad_strip_kernel<true>, dim3(nb), dim3(256), 0, s, x, dy, part, dbias ? bias_part : (float*)nullptr, g);
+        else hipLaunchKernelGGL(wgrad_strip_kernel<false>, dim3(nb), dim3(256), 0, s, x, dy, part, dbias ? bias_part : (float*)nullptr, g);
     }
     GX_CHECK_LAUNCH("gx_conv3x3_wgrad_quad(strips)");
     {

@@ -55,18 +55,18 @@ def step_state():
 
 def ctx_bound(cls):
     """Class decorator for the autograd Functions: backward runs in the library context of its forward, and at the matmul
-    precision level of its forward (genesis_amd.precision: a change in between raises)."""
+    precision level and tap-conv mode of its forward (genesis_amd.precision.key: a change in between raises)."""
     fwd, bwd = cls.forward, cls.backward
 
     def forward(ctx, *args):
         ctx._gx_ctx = _lib.current_ctx()
-        ctx._gx_level = _precision.level()
+        ctx._gx_level = _precision.key()
         if _DEBUG_SYNC:
             torch.cuda.synchronize()
         return fwd(ctx, *args)
 
     def backward(ctx, *grads):
-        _precision.check_backward(ctx._gx_level)
+        _precision.check_backward_key(ctx._gx_level)
         prev = _lib.current_ctx()
         _lib.make_current(ctx._gx_ctx)
         if _DEBUG_SYNC:

@@ -103,7 +103,7 @@ class TrainStep(object):
         self._static_x = None
         self._out = None
         self.iters = 0
-        self._level = _precision.level()      # the matmul precision level the weight cache / graphs were built at
+        self._level = _precision.key()        # the matmul precision level and tap-conv mode the weight cache / graphs were built at
         self.sync_from_rank0()
 
     # ------------------------------------------------------------------ flat buffers
@@ -510,10 +510,10 @@ class TrainStep(object):
             self.graph2.replay()
 
     def _follow_level(self):
-        """The matmul precision level changed since the weight cache was recorded / the graphs were captured
-        (genesis_amd.set_matmul_precision): both hold the old level's packings and kernels.  The cache is recorded afresh by
-        the next iteration and the graphs are RE-CAPTURED by the next step() -- never replayed stale."""
-        lv = _precision.level()
+        """The matmul precision level or the tap-conv mode changed since the weight cache was recorded / the graphs were
+        captured (genesis_amd.set_matmul_precision / set_tapconv_precision): both hold the old packings and kernels.  The cache
+        is recorded afresh by the next iteration and the graphs are RE-CAPTURED by the next step() -- never replayed stale."""
+        lv = _precision.key()
         if lv == self._level:
             return
         if self._wcache is not None:
@@ -526,7 +526,8 @@ class TrainStep(object):
     def step(self, x, **forward_kwargs):
         """x [B,3,S,S] on the device.  Returns a device tensor [elbo, err, kl, beta_used] (no host sync).
         forward_kwargs (rand_pixel / eps / seed_idx injection, parity tests) force the eager path.  After a change of the
-        matmul precision level the next call re-records the weight cache and, with graph=True, re-captures the step."""
+        matmul precision level or the tap-conv mode the next call re-records the weight cache and, with graph=True, re-captures
+        the step."""
         self._follow_level()
         if self.use_graph and not forward_kwargs:
             if self.graph is None:

@@ -123,8 +123,9 @@ int gx_kq_precision(int mode);
  *                     the relative error of one bf16 product -- two roundings of 2^-9 each, about 2^-8 per product -- and fp32's
  *                     exponent range (no per-tensor scale: the partial-maxima hints of gx_amax_tap / gx_kq_amax_link /
  *                     gx_conv_input_amax / gx_wgq_operand_amax are not needed and are ignored when present); sums of many such
- *                     products are accumulated in fp32.  Layers on the fp32 pipe in every mode stay there: the small-level tap
- *                     convs, gx_igemm, gx_wstrip, the broadcast convs, dense layers, the LSTM.
+ *                     products are accumulated in fp32.  The small-level tap convs and gx_wstrip are NOT switched by this level:
+ *                     gx_tapconv_precision below is their own opt-in.  Layers on the fp32 pipe in every mode stay there: gx_igemm,
+ *                     the broadcast convs, dense layers, the LSTM.
  *        -1         -- every family back to its environment default.
  *      Returns the level in force BEFORE the call, or GX_MATMUL_MIXED when the three families' modes are not one level (set one by
  *      one, or by the per-family environment variables); negative: error.  gx_matmul_precision_get() returns the current level
@@ -134,6 +135,28 @@ int gx_kq_precision(int mode);
 #define GX_MATMUL_MIXED 3
 int gx_matmul_precision(int level);
 int gx_matmul_precision_get(void);
+/*      The arithmetic of the tap-conv kernels (gx_conv.hip: tapconv_kernel in every mode and tapconv_dt_kernel -- the layers of
+ *      gx_conv3x3_fwd / _bias_act_fwd / _dgrad, gx_deconv5x5s2_fwd / _gn_stats_fwd / _dgrad and gx_conv5x5s1 that the 16-bit-pipe
+ *      families do not take) and of the strip weight gradient (gx_wstrip.hip: gx_conv3x3_wgrad_quad / _bias on grids that are no
+ *      power of two), a switch of its own beside gx_matmul_precision:
+ *        0  -- the default: the tap-conv kernels multiply on the fp32 pipe (v_mfma_f32_32x32x2_f32), the strips from six bf16 piece
+ *              products (fp32 accuracy);
+ *        3  -- medium: every operand rounded ONCE to bf16 (round to nearest even) -- the packed weights one bf16 plane (pack kinds
+ *              70 ..), the input halo tile converted on its way into LDS, one v_mfma_f32_32x32x16_bf16 per k-step (two taps x 8
+ *              channels), fp32 accumulation; the strips split every window row and dy value into one piece and issue one MFMA per
+ *              tap.  About 2^-8 relative error per product, fp32's exponent range.  Split-K partials, their reduce launches and the
+ *              strips' two fixed-order reduce launches are unchanged: results stay bit-reproducible.  The input is staged through
+ *              registers in this mode (LDS-DMA cannot convert).  A transposed conv's data gradient whose halo tile the bf16 stage
+ *              cannot hold (1-pixel grids) runs mode 0, and gx_tapconv_last_mode() says so.
+ *        -1 -- back to the environment's default (GENESIS_TAPCONV_PRECISION=default|medium; unset: 0).
+ *      Returns the mode in force BEFORE the call; negative: error.  Independent of gx_matmul_precision: neither reads nor writes
+ *      the other.  Out of scope (unchanged in every mode): wgrad_fast_kernel, conv3x3s2_wgrad_small_kernel, gx_igemm, the dense /
+ *      LSTM kernels and the broadcast convs.  Packed weights are laid out per mode (a weight cache recorded in one mode never
+ *      serves the other): switch between iterations, not inside one.
+ *      gx_tapconv_last_mode(): the mode (0 or 3) of this thread's most recent tap-conv or strip launch, -1 if there was none. */
+int gx_tapconv_precision(int mode);
+int gx_tapconv_precision_get(void);
+int gx_tapconv_last_mode(void);
 /*      Mode 2's per-tensor maximum without a second pass over the tensor: gx_kq_amax_link(parts, capacity, numel) arms a one-shot,
  *      per-thread hand-over -- the next producer that supports it (the register-resident GroupNorm + ReLU kernels behind gx_gn_relu_fwd_parts /
  *      gx_gn_relu_bwd_parts and the decoder head's backward behind gx_gn_relu_bwd_proj: models/genesisv2_config.py:90-99) writes one partial maximum of the gradient it stores
