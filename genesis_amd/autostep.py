@@ -93,7 +93,7 @@ def _wrapped_or_threaded(model):
       would carry zeros and be copied back over the flushed gradients.  Under a DDP forward the plain path runs."""
     if getattr(model, '_is_replica', False) or threading.current_thread() is not threading.main_thread():
         return True
-    return _DDP._active_ddp_module is not None
+    return getattr(_DDP, '_active_ddp_module', None) is not None
 
 
 def arm(model, x=None):
@@ -265,18 +265,21 @@ def end_backward():
 # HOST: ~170 ctypes launches + autograd bookkeeping per iteration issue more slowly than the GPU executes them.
 # From the third iteration of a steady loop on -- same input shape, same parameters, no injected noise -- the model therefore
 #   * captures its forward pass (the packed-weight refresh included) into ONE HIP graph on a private copy of the input and, in every
-#     later iteration, copies x in, replays it and returns the SAME static output tensors, re-wrapped as the outputs of one autograd
-#     node (`_ReplayFn`) -- to the loop they are ordinary tensors that require grad;
-#   * captures, at the first `loss.backward()` that reaches that node with gradients for the loss terms only (err, the KL terms:
-#     train.py:226-242), the whole backward pass -- zeroed flat gradient buffer, direct gradient writes, ONE stream-K weight-gradient
+#     later iteration, copies x in, replays it and returns the SAME static output tensors; every one that required grad at capture
+#     (the loss terms, mu, sigma, z, the masks, recon, x_r, log_m_r, ...) is re-wrapped as an output of one autograd node
+#     (`_ReplayFn`) -- to the loop they are ordinary tensors that require grad;
+#   * captures, at the first `loss.backward()` that reaches that node (normally with gradients for the loss terms only: err, the
+#     KL terms, train.py:226-242), the whole backward pass for that set of outputs -- zeroed flat gradient buffer, direct gradient writes, ONE stream-K weight-gradient
 #     launch, batched reductions -- into a second graph, and replays it from then on after copying the incoming gradients into
 #     static buffers.  p.grad are views of the flat buffer, as above; `torch.optim.*.step()` consumes them as usual.
 # The loop's contract is untouched: `optimiser.zero_grad(); model(x); ...; loss.backward(); optimiser.step()`.  What differs from the
 # eager path and is documented here: the returned tensors are overwritten by the next forward (train.py reads what it logs before
 # that: `.item()`, train.py:266-270).  Everything else falls back -- and stays correct: gradients already present at backward
-# time (accumulation) or gradients arriving for other outputs (a loss built on `recon`) run the ordinary autograd backward of the
-# captured forward's own (retained) graph on the static tensors; a changed input shape, moved / replaced parameters, eval mode,
-# no_grad, injected noise, dynamic_K, a TrainStep in the same context, DataParallel / DDP wrappers take the eager path above.
+# time (accumulation) or a set of outputs with gradients other than the captured one (a loss that also reads `recon` or
+# `comp_stats.z_k`) run the ordinary autograd backward of the captured forward's own (retained) graph from those outputs, on the
+# static tensors; a changed input shape, moved / replaced / frozen parameters, a changed scalar setting (_SETTINGS, the attention
+# kernel), eval mode, no_grad, injected noise, dynamic_K, a TrainStep in the same context, DataParallel / DDP wrappers take the eager
+# path above.
 # GENESIS_AUTOSTEP_GRAPH=0 switches this stage off.
 GRAPH = os.environ.get('GENESIS_AUTOSTEP_GRAPH', '1') != '0'
 _STABLE_ITERS = 2          # eager (armed) iterations with the same key before the capture
@@ -306,9 +309,18 @@ def graph_stats(model):
     return (g.replays, g.bwd_replays, g.bwd_fallbacks) if g is not None else (0, 0, 0)
 
 
+# The model's scalar settings a captured forward bakes in (read by _compute, _decode, _component_kl as Python values).
+_SETTINGS = ('klm_loss', 'detach_mr_in_klm', 'pixel_bound', 'autoreg_prior', 'std')
+
+
 def _graph_key(model, x):
-    # (the matmul precision level and tap-conv mode: a graph captured under others holds their kernels and packings)
-    return (tuple(x.shape), x.dtype, x.device, _param_key(model), bool(getattr(model, 'klm_loss', False)), _precision.key())
+    # the parameters with their requires_grad flags (the captured backward writes a gradient for every parameter it captured),
+    # the settings above, the attention kernel, and the matmul precision level and tap-conv mode (a graph captured under others
+    # holds their kernels and packings)
+    ap = getattr(model, 'att_process', None)
+    return (tuple(x.shape), x.dtype, x.device, tuple((id(p), p.data_ptr(), p.requires_grad) for p in _params(model)),
+            tuple(getattr(model, k, None) for k in _SETTINGS), getattr(ap, 'kernel', None), getattr(ap, 'semiconv', None),
+            _precision.key())
 
 
 def _drop_graph(g):
@@ -318,7 +330,8 @@ def _drop_graph(g):
 
 
 class _ReplayFn(torch.autograd.Function):
-    """The captured forward's loss terms as the outputs of ONE autograd node; its backward is the captured backward graph."""
+    """Every captured output that required grad (the loss terms, mu, sigma, z, the masks, the decoder outputs, ...) as the outputs
+    of ONE autograd node; its backward is the captured backward graph, or the retained-graph fallback for another pattern."""
 
     @staticmethod
     def forward(ctx, dummy, g):
@@ -409,7 +422,8 @@ def _capture_forward(model, x, g, cache_id, book):
             _lib.call('gx_weight_cache_release')
     g.meta = {k: v for k, v in t.items() if not torch.is_tensor(v)}
     g.tensors = {k: v for k, v in t.items() if torch.is_tensor(v)}
-    g.root_names = [k for k in ('err', 'kl', 'kl_m') if k in g.tensors and g.tensors[k].requires_grad]
+    # (every output a gradient can reach: one left out would come back detached and its gradient would be lost)
+    g.root_names = [k for k, v in g.tensors.items() if v.requires_grad]
     g.roots = [g.tensors[k] for k in g.root_names]
     g.F, g.B, g.bpattern = F, None, None
     F.replay()                      # (a capture executes nothing)

@@ -218,6 +218,15 @@ def _ret(out, value):
     return None if out is not None else value
 
 
+def _refuse_grads(fn_name, grads, names=('log_s', 'colour', 'seeds')):
+    """The IC-SBP by-products log_s (stats.log_s_k), colour (att_stats.colour) and seeds (att_stats.seeds) are differentiable in
+    the reference, but their kernels have no backward: a gradient that reaches one of them raises instead of being dropped."""
+    for name, g in zip(names, grads):
+        if g is not None:
+            raise RuntimeError('%s: a gradient reached the IC-SBP output %r, which has no backward here; detach it '
+                               'before building a loss on it' % (fn_name, name))
+
+
 @ctx_bound
 class ConvGNReLUFn(torch.autograd.Function):
     @staticmethod
@@ -416,7 +425,7 @@ class ICSBPFn(torch.autograd.Function):
         ctx.nsteps = res[4] if min_mass > 0.0 else None
         ctx.save_for_backward(feat, conv_w, conv_b, gate, log_sigma, colour, seeds, idx)
         ctx.kernel = kernel
-        ctx.mark_non_differentiable(log_s, colour, seeds, idx)
+        ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)   # no zero-filled gradients for the outputs nobody differentiates
         if ctx.nsteps is not None:
             ctx.mark_non_differentiable(ctx.nsteps)
@@ -424,7 +433,8 @@ class ICSBPFn(torch.autograd.Function):
         return log_m, log_s, colour, seeds, idx
 
     @staticmethod
-    def backward(ctx, g_log_m, *unused):
+    def backward(ctx, g_log_m, *rest):
+        _refuse_grads('ICSBPFn', rest)
         feat, conv_w, conv_b, gate, log_sigma, colour, seeds, idx = ctx.saved_tensors
         if g_log_m is None:       # log_m unused downstream
             g_log_m = colour.new_zeros(seeds.shape[0] + 1, colour.shape[0], 1, colour.shape[2], colour.shape[3])
@@ -469,7 +479,7 @@ class SegICSBPFn(torch.autograd.Function):
         ctx.nsteps = res[4] if min_mass > 0.0 else None
         ctx.save_for_backward(x, y, mean, rstd, ls64, colour, seeds, idx)
         ctx.kernel = kernel
-        ctx.mark_non_differentiable(log_s, colour, seeds, idx)
+        ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
         if ctx.nsteps is not None:
             ctx.mark_non_differentiable(ctx.nsteps)
@@ -477,7 +487,8 @@ class SegICSBPFn(torch.autograd.Function):
         return log_m, log_s, colour, seeds, idx
 
     @staticmethod
-    def backward(ctx, g_log_m, *unused):
+    def backward(ctx, g_log_m, *rest):
+        _refuse_grads('SegICSBPFn', rest)
         x, y, mean, rstd, ls64, colour, seeds, idx = ctx.saved_tensors
         seg_w, seg_gamma, seg_beta, conv_w, conv_b, gate, log_sigma = ctx.params
         if g_log_m is None:
@@ -538,7 +549,7 @@ class SegFeatHeadsFn(torch.autograd.Function):
         meanf, rstdf = hip.gn_relu_fwd(yf, feat_gamma, feat_beta, GROUPS, EPS, (f, 0, 0))
         ctx.save_for_backward(x, y, mean, rstd, ls64, colour, seeds, idx, yf, meanf, rstdf)
         ctx.kernel = kernel
-        ctx.mark_non_differentiable(log_s, colour, seeds, idx)
+        ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
         if ctx.nsteps is not None:
             ctx.mark_non_differentiable(ctx.nsteps)
@@ -547,6 +558,7 @@ class SegFeatHeadsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_log_m, *rest):
+        _refuse_grads('SegFeatHeadsFn', rest)
         x, y, mean, rstd, ls64, colour, seeds, idx, yf, meanf, rstdf = ctx.saved_tensors
         seg_w, seg_gamma, seg_beta, conv_w, conv_b, gate, log_sigma, feat_w, feat_gamma, feat_beta = ctx.params
         g_f = rest[-1]
@@ -731,9 +743,39 @@ class DecoderFn(torch.autograd.Function):
         return (dz, None) + tuple(grads)
 
 
+def _fold_output_grads(dec, K, pixel_bound, g_recon, g_x_r, g_log_m_r, log_w=None):
+    """The gradient on dec [K*B,C,H,W] (and on log_w [K,B,1,H,W]) of the mixture's by-product outputs, recomputed from dec with
+    plain torch ops: x_r = sigmoid (pixel_bound) or identity of channels 0-2, log_m_r = log_softmax over K of channel 3 (unless
+    the mixing log-weights come in as log_w), recon = sum_k exp(log_m_r) x_r.  None where no such gradient arrived."""
+    if g_recon is None and g_x_r is None and g_log_m_r is None:
+        return None, None
+    N, C, H, W = dec.shape
+    d = dec.view(K, N // K, C, H, W)
+    a = d[:, :, :3]
+    x_r = torch.sigmoid(a) if pixel_bound else a
+    lm = torch.log_softmax(d[:, :, 3:4], 0) if log_w is None else log_w
+    m = lm.exp()
+    dx = torch.zeros_like(x_r) if g_x_r is None else g_x_r.clone()
+    dlm = None if g_log_m_r is None else g_log_m_r.clone()
+    if g_recon is not None:
+        dx = dx + m * g_recon.unsqueeze(0)
+        t = (m * x_r * g_recon.unsqueeze(0)).sum(2, keepdim=True)
+        dlm = t if dlm is None else dlm + t
+    if pixel_bound:
+        dx = dx * x_r * (1.0 - x_r)
+    ddec = torch.zeros_like(d)
+    ddec[:, :, :3] = dx
+    if log_w is None:
+        if dlm is not None:
+            ddec[:, :, 3:4] = dlm - m * dlm.sum(0, keepdim=True)
+        return ddec.view(N, C, H, W), None
+    return ddec.view(N, C, H, W), dlm
+
+
 @ctx_bound
 class MixtureFn(torch.autograd.Function):
-    """returns (err [B], recon [B,3,H,W], x_r [K,B,3,H,W], log_m_r [K,B,1,H,W])."""
+    """returns (err [B], recon [B,3,H,W], x_r [K,B,3,H,W], log_m_r [K,B,1,H,W]), all differentiable w.r.t. dec.  A gradient on err
+    alone is the kernel's backward; one on recon, x_r or log_m_r is added by _fold_output_grads."""
 
     @staticmethod
     def forward(ctx, x, dec, K, pixel_std, pixel_bound):
@@ -742,17 +784,21 @@ class MixtureFn(torch.autograd.Function):
         err, recon, x_r, log_m_r = hip.mixture_fwd(x, dec, K, pixel_std, pixel_bound)
         ctx.save_for_backward(x, dec)
         ctx.cfg = (K, pixel_std, pixel_bound)
-        ctx.mark_non_differentiable(recon, x_r, log_m_r)
         ctx.set_materialize_grads(False)
         return err, recon, x_r, log_m_r
 
     @staticmethod
-    def backward(ctx, g_err, *unused):
+    def backward(ctx, g_err, g_recon, g_x_r, g_log_m_r):
         x, dec = ctx.saved_tensors
         K, pixel_std, pixel_bound = ctx.cfg
+        extra, _ = _fold_output_grads(dec, K, pixel_bound, g_recon, g_x_r, g_log_m_r)
         if g_err is None:
+            if extra is not None:
+                return None, extra, None, None, None
             g_err = x.new_zeros(x.shape[0])
         ddec = hip.mixture_bwd(x, dec, g_err.contiguous(), K, pixel_std, pixel_bound)
+        if extra is not None:
+            ddec += extra
         return None, ddec, None, None, None
 
 
@@ -1030,7 +1076,8 @@ def _wgrad_paired(h, dy, gw, gb=None):
 @ctx_bound
 class MixtureWFn(torch.autograd.Function):
     """Mixture likelihood with the ATTENTION masks as mixing weights (models/monet_config.py:94-105).
-    returns (err [B], recon [B,3,H,W], x_r [K,B,3,H,W]); differentiable w.r.t. dec and log_w."""
+    returns (err [B], recon [B,3,H,W], x_r [K,B,3,H,W]); all differentiable w.r.t. dec and log_w (recon and x_r through
+    _fold_output_grads)."""
 
     @staticmethod
     def forward(ctx, x, dec, log_w, K, std1, std2, pixel_bound):
@@ -1038,17 +1085,23 @@ class MixtureWFn(torch.autograd.Function):
         err, recon, x_r = hip.mixture_w_fwd(x, dec, log_w, K, std1, std2, pixel_bound)
         ctx.save_for_backward(x, dec, log_w)
         ctx.cfg = (K, std1, std2, pixel_bound)
-        ctx.mark_non_differentiable(recon, x_r)
         ctx.set_materialize_grads(False)
         return err, recon, x_r
 
     @staticmethod
-    def backward(ctx, g_err, *unused):
+    def backward(ctx, g_err, g_recon, g_x_r):
         x, dec, log_w = ctx.saved_tensors
         K, std1, std2, pixel_bound = ctx.cfg
+        extra, extra_w = _fold_output_grads(dec, K, pixel_bound, g_recon, g_x_r, None, log_w)
         if g_err is None:
+            if extra is not None:
+                return None, extra, extra_w, None, None, None, None
             g_err = x.new_zeros(x.shape[0])
         ddec, dlog_w = hip.mixture_w_bwd(x, dec, log_w, g_err.contiguous(), K, std1, std2, pixel_bound)
+        if extra is not None:
+            ddec += extra
+            if extra_w is not None:
+                dlog_w += extra_w
         return None, ddec, dlog_w, None, None, None, None
 
 

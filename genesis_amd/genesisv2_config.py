@@ -226,9 +226,9 @@ class GenesisV2(nn.Module):
         return p
 
     def _decode(self, z_kbd, x=None, grad_through_masks=False):
-        """z [K,B,D] -> (dec [K*B,4,H,W]) -> mixture.  Returns (err, recon, x_r [K,...], log_m_r [K,...]).
-        grad_through_masks: log_m_r carries a gradient back into the decoder (the mixture kernel's own outputs are
-        non-differentiable by-products)."""
+        """z [K,B,D] -> (dec [K*B,4,H,W]) -> mixture.  Returns (err, recon, x_r [K,...], log_m_r [K,...]), all differentiable.
+        grad_through_masks: a gradient on log_m_r goes through the log-softmax backward kernel (MaskReconFn, the mask KL's path
+        when it does not detach the reconstructed masks) instead of MixtureFn's plain-torch fold."""
         K, B, D = z_kbd.shape
         _, dec_coords = self._grid(z_kbd.device)
         dec = fn.DecoderFn.apply(z_kbd.reshape(K * B, D), dec_coords, *self._decoder_params())

@@ -340,7 +340,7 @@ def test_unchanged_loop_as_two_replayed_graphs_equals_the_eager_loop(case):
 
 
 def test_graph_loop_falls_back_and_stays_correct():
-    """Gradient accumulation (no zero_grad between two backward passes), a loss that also reads `recon`, an evaluation forward
+    """Gradient accumulation (no zero_grad between two backward passes), a loss that also reads `recon`, `mu_k` or `z_k`, an evaluation forward
     and a changed batch size in the middle of a captured loop: each takes the ordinary autograd path and gives the gradients
     the eager loop gives."""
     from genesis_amd import autostep
@@ -363,6 +363,12 @@ def test_graph_loop_falls_back_and_stays_correct():
             torch.manual_seed(5)
             recon, losses, *_ = model(xd)
             (losses.err.mean(0) + recon.pow(2).mean()).backward()
+        elif scenario in ('mu_loss', 'z_loss'):
+            # (a loss term on a latent: in the replayed form mu and z come back through the replay node, not detached)
+            torch.manual_seed(5)
+            _, losses, _, _, comp = model(xd)
+            lat = torch.stack(comp.mu_k if scenario == 'mu_loss' else comp.z_k)
+            (losses.err.mean(0) + torch.stack(losses.kl_l_k, dim=1).mean(dim=0).sum() + lat.pow(2).sum() / lat.shape[1]).backward()
         elif scenario == 'eval_between':
             model.eval()
             with torch.no_grad():
@@ -380,7 +386,7 @@ def test_graph_loop_falls_back_and_stays_correct():
 
     try:
         autostep.ENABLED = True
-        for scenario in ('accumulate', 'recon_loss', 'eval_between', 'other_batch'):
+        for scenario in ('accumulate', 'recon_loss', 'mu_loss', 'z_loss', 'eval_between', 'other_batch'):
             g0 = grads_after(build(gold), False, scenario)
             model = build(gold)
             g1 = grads_after(model, True, scenario)
@@ -390,7 +396,7 @@ def test_graph_loop_falls_back_and_stays_correct():
                 assert float((g0[n].double() - g1[n].double()).norm()) / den <= 5e-5, (scenario, n)
             fwd, bwd, fb = autostep.graph_stats(model)
             assert fwd >= 2, (scenario, fwd)
-            if scenario in ('accumulate', 'recon_loss'):
+            if scenario in ('accumulate', 'recon_loss', 'mu_loss', 'z_loss'):
                 assert fb >= 1, (scenario, fb)
             _state_is_clean()
     finally:
