@@ -8,11 +8,15 @@
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM: zero grads,
 GenesisV2.forward (HIP kernels), loss aggregation, GECO, backward (HIP kernels), [RCCL all-reduce of the
 flat gradient bucket], fused Adam.  Weak scaling: per-GPU batch fixed (default 32, train.py:48).
-Rank 0 prints ONE JSON line; besides the driver's contract it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+driver's contract (metric, value, unit, ms_per_step, ...) -- nothing else.  With --full it also runs the legs after the
+timed region and carries what they measure, among them
   roofline     -- the dominant kernel's achieved rate from HIP events recorded around every launch of it
                   during extra profiled steps in this same process (gx_profile_*), vs the gfx950 peak;
   cpu_baseline -- the oracle (CPU restatement of the reference, reference-equivalent form) timed on this
-                  host's cores on a bounded sample of the same workload (rank 0, N=1 only).
+                  host's cores on a bounded sample of the same workload (rank 0, N=1 only);
+and steady_state, value_structured_inputs, the all-reduce timing (N > 1), pcie_inclusive, value_fp32_pipe_only,
+value_as_written and value_reference_loop.
 """
 import argparse
 import json
@@ -47,16 +51,22 @@ def parse():
     ap.add_argument('--model', default='genesisv2', choices=['genesisv2', 'monet', 'genesis', 'vae'],
                     help='genesisv2 = the BASELINE metric; monet / genesis / vae = BASELINE configs 4 / 3 / 1 (informational)')
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of HIP-graph replay')
-    ap.add_argument('--profile-steps', type=int, default=3)
-    ap.add_argument('--cpu-seconds', type=float, default=15.0, help='budget of the CPU baseline leg (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, run every other leg as well (steady_state, value_structured_inputs, the '
+                         'all-reduce timing, roofline, pcie_inclusive, value_fp32_pipe_only, value_as_written, '
+                         'value_reference_loop, cpu_baseline; the options below size them); without it a run does only what '
+                         'value and ms_per_step need')
+    ap.add_argument('--profile-steps', type=int, default=3, help='--full: eager profiled steps of the roofline leg (0 = skip)')
+    ap.add_argument('--cpu-seconds', type=float, default=15.0, help='--full: budget of the CPU baseline leg (0 = skip)')
     ap.add_argument('--fp32-pipe-steps', type=int, default=30,
-                    help='extra leg on rank 0 at N=1: steps with every product on the fp32 matrix pipe (gx_wgq_precision(0), '
+                    help='--full: extra leg on rank 0 at N=1: steps with every product on the fp32 matrix pipe (gx_wgq_precision(0), '
                          'gx_kq_precision(0)), reported as value_fp32_pipe_only, never as value; 0 = skip')
     ap.add_argument('--extra-leg-steps', type=int, default=30,
-                    help='extra legs on rank 0 at N=1: value_as_written (the step + mse / rmse + the forward outputs no loss reads) '
-                         'and value_reference_loop (train.py:223-263 unchanged, eager, torch.optim.Adam); 0 = skip')
+                    help='--full: extra legs on rank 0 at N=1: value_structured_inputs, value_as_written (the step + mse / rmse + '
+                         'the forward outputs no loss reads) and value_reference_loop (train.py:223-263 unchanged, eager, '
+                         'torch.optim.Adam); 0 = skip')
     ap.add_argument('--host-input-steps', type=int, default=100,
-                    help='extra leg on rank 0 at N=1: steps fed from uint8 frames in host memory through the PCIe feeder '
+                    help='--full: extra leg on rank 0 at N=1: steps fed from uint8 frames in host memory through the PCIe feeder '
                          '(reported as pcie_inclusive, never as value; 0 = skip)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy, float32 / '
@@ -351,7 +361,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # (the legs below step the same model on: what the last timed step computed is copied out now, outside the timed region)
+    # (the --full legs below step the same model on: what the last timed step computed is copied out now, outside the timed
+    # region)
     dumped = step_outputs(ts, out) if args.dump_outputs and rank == 0 else None
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
@@ -359,10 +370,12 @@ def main():
     dt = float(tmax)
     elbo = float(out[0])
 
+    # ---- from here on every GPU or CPU leg runs with --full only; a plain run just assembles the result line
+
     # a longer window of the SAME loop (SURVEY.md 8d asks for >= 100 timed steps; the driver's command times 20): every rank
     # runs it (the collective inside the step needs all of them), bracketed like the timed region; reported as
     # `steady_state`, never as `value`
-    long_steps = int(os.environ.get('GENESIS_BENCH_LONG_STEPS', '200'))
+    long_steps = int(os.environ.get('GENESIS_BENCH_LONG_STEPS', '200')) if args.full else 0
     dt_long = None
     if long_steps > args.steps:
         torch.cuda.synchronize()
@@ -386,7 +399,7 @@ def main():
     # exact zeros / ones and constant regions.  Reported as `value_structured_inputs`, never as `value`; parity on this input
     # set: tests/golden/full_v2_metric_b32_rect.npz.
     dt_rect = None
-    if world == 1 and args.model == 'genesisv2' and args.extra_leg_steps > 0:
+    if args.full and world == 1 and args.model == 'genesisv2' and args.extra_leg_steps > 0:
         from genesis_amd.testing import make_rect_input
         rect = [make_rect_input(4321 + i, args.batch, args.img).to(device) for i in range(4)]
         for i in range(5):
@@ -403,7 +416,7 @@ def main():
     # the bucket is zeroed first and is clean afterwards, as the step leaves it).  In the step it is exposed by construction
     # (DESIGN.md section 6), so this is what one step pays for it.
     ar_ms = None
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         with torch.no_grad():
             ts.bucket.zero_grad()
             for _ in range(3):
@@ -475,9 +488,10 @@ def main():
                                               'bytes_per_all_reduce': int(ts.bucket.flat_g.numel() * 4),
                                               'all_reduce_ms': ar_ms,
                                               'all_reduce_share_of_step': ar_ms / (1e3 * dt / args.steps) if ar_ms else None,
-                                              'all_reduce_timing': '20 back-to-back all-reduces of the bucket on an idle GPU after '
-                                                                   'the timed region (host clock around a synchronised loop, max '
-                                                                   'over ranks); inside the step the collective is not overlapped'}
+                                              'all_reduce_timing': ('20 back-to-back all-reduces of the bucket on an idle GPU after '
+                                                                    'the timed region (host clock around a synchronised loop, max '
+                                                                    'over ranks); inside the step the collective is not overlapped')
+                                                                   if ar_ms is not None else 'not measured (bench.py --full)'}
         if flop_img:
             result['step_fraction_of_fp32_mfma_peak'] = value / world * flop_img / (PEAK_FP32_MFMA_TFLOPS * 1e12)
         if dumped is not None:
@@ -485,7 +499,7 @@ def main():
             del dumped
 
     # ---- roofline leg: HIP events around every kernel launch, eager steps, same process (rank 0)
-    if rank == 0 and args.profile_steps > 0 and world == 1:
+    if args.full and rank == 0 and args.profile_steps > 0 and world == 1:
         ts.use_graph = False
         ts._iteration(batches[0])  # eager warm-up after graph mode
         torch.cuda.synchronize()
@@ -609,7 +623,7 @@ def main():
     # ---- PCIe-inclusive leg: every batch starts as uint8 HWC frames in host memory (what a dataset yields) and
     #      travels through genesis_amd.feeder (pinned staging, copy one batch ahead on a side stream, one conversion
     #      launch).  Reported next to `value`, never as `value`.
-    if rank == 0 and world == 1 and args.host_input_steps > 0 and ts.graph is not None:
+    if args.full and rank == 0 and world == 1 and args.host_input_steps > 0 and ts.graph is not None:
         from genesis_amd.feeder import DeviceFeeder
         ts.use_graph = True
         n_warm = 40            # the host has to get ~30 graph launches ahead of the device before the rate is steady
@@ -638,7 +652,7 @@ def main():
     # ---- fp32-pipe-only leg: the same step with the bf16-pipe kernels (six bf16 piece products per fp32 product) switched
     #      back to v_mfma_f32_32x32x2_f32; a second TrainStep (own HIP graph) on the same model.  Last GPU leg: it re-flattens
     #      the parameters.
-    if rank == 0 and world == 1 and args.fp32_pipe_steps > 0 and args.model == 'genesisv2' and not args.no_graph and \
+    if args.full and rank == 0 and world == 1 and args.fp32_pipe_steps > 0 and args.model == 'genesisv2' and not args.no_graph and \
             os.environ.get('GENESIS_WGQ_BF16X6', '1') != '0' and os.environ.get('GENESIS_KQ_BF16X6', '1') != '0':
         from genesis_amd import _lib
         ts.close()
@@ -669,7 +683,7 @@ def main():
     # ---- what the timed step leaves out of the reference's iteration, priced: train.py:244-246 computes mse / rmse
     #      every iteration and GenesisV2.forward builds mx_r_k / instance_seg / instance_seg_r (genesisv2_config.py:184-188) and
     #      att_stats.delta unconditionally; none of them feeds the loss, `value` computes them on first access only.
-    if rank == 0 and world == 1 and args.extra_leg_steps > 0 and args.model == 'genesisv2' and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and args.extra_leg_steps > 0 and args.model == 'genesisv2' and not args.no_graph:
         ts.close()
         ts3 = TrainStep(model, args.img, lr=1e-4, graph=True, log_mse=True, materialise_stats=True)
         ts3.prepare(batches[0])
@@ -694,7 +708,7 @@ def main():
     #      loss.backward(); torch.optim.Adam.step() -- issued eagerly from Python, one host read per iteration where
     #      utils/geco.py:45 has its `.item()`.  What a maintainer gets WITHOUT adopting TrainStep; `value` is TrainStep's graph.
     #      (genesis_amd/autostep.py gives this loop TrainStep's launch structure without the loop knowing.)
-    if rank == 0 and world == 1 and args.extra_leg_steps > 0 and args.model == 'genesisv2':
+    if args.full and rank == 0 and world == 1 and args.extra_leg_steps > 0 and args.model == 'genesisv2':
         from genesis_amd.geco import make_geco
         torch.cuda.synchronize()
         model_r = build_model(args, device)
@@ -748,7 +762,7 @@ def main():
                                          'outputs no loss reads are off: priced in value_as_written); the unchanged train.py loop on the '
                                          'same model: value_reference_loop')
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and args.model == 'genesisv2':
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and args.model == 'genesisv2':
         result['cpu_baseline'] = cpu_baseline(args)
         result['speedup_vs_cpu_baseline'] = result['value'] / result['cpu_baseline']['value']
     if rank == 0:

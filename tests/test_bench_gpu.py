@@ -1,5 +1,5 @@
-"""bench.py contract: ONE JSON line with the driver's keys, the roofline object (HIP events around the dominant kernel
-inside the same process) and the CPU baseline object; the timed value comes from HIP-graph replay."""
+"""bench.py contract: ONE JSON line with the driver's keys; with --full also the roofline object (HIP events around the
+dominant kernel inside the same process) and the CPU baseline object; the timed value comes from HIP-graph replay."""
 import json
 import os
 import os.path as osp
@@ -15,7 +15,7 @@ ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
 @pytest.mark.timeout(600)
 def test_bench_line_contract():
     env = dict(os.environ, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, osp.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--cpu-seconds', '2',
+    out = subprocess.run([sys.executable, osp.join(ROOT, 'bench.py'), '--full', '--steps', '4', '--warmup', '2', '--cpu-seconds', '2',
                           '--profile-steps', '1', '--host-input-steps', '3', '--extra-leg-steps', '3'], capture_output=True, text=True, env=env,
                          cwd=ROOT, timeout=580)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -46,6 +46,30 @@ def test_bench_line_contract():
     assert 'value_reference_loop' in d['config']['workload']
 
 
+FULL_ONLY = ('steady_state', 'value_structured_inputs', 'roofline', 'roofline_top', 'kernels', 'pcie_inclusive',
+             'value_fp32_pipe_only', 'value_as_written', 'value_reference_loop', 'cpu_baseline', 'speedup_vs_cpu_baseline')
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_the_timed_steps_only():
+    """Without --full the run is set-up, warm-up, the timed steps and the result line: the driver's keys, none of the legs."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    env.pop('GENESIS_BENCH_LONG_STEPS', None)
+    out = subprocess.run([sys.executable, osp.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2'], capture_output=True,
+                         text=True, env=env, cwd=ROOT, timeout=280)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+              'vs_baseline', 'dtype', 'data', 'config', 'final_elbo'):
+        assert k in d, k
+    assert d['n_gpus'] == 1 and d['steps'] == 4 and d['warmup'] == 2 and d['higher_is_better'] is True
+    assert d['unit'] == 'images/sec' and d['dtype'] == 'f32' and d['config']['launch'] == 'hip-graph'
+    assert d['value'] > 0 and abs(d['value'] - 32 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    assert [k for k in FULL_ONLY if k in d] == []
+
+
 @pytest.mark.timeout(900)
 def test_bench_two_rank_launch_rehearsal():
     """The driver's N > 1 command line (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N) on the
@@ -57,7 +81,7 @@ def test_bench_two_rank_launch_rehearsal():
     env = dict(os.environ, PYTHONPATH=ROOT, GENESIS_BENCH_REHEARSAL='1', GENESIS_BENCH_LONG_STEPS='0')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                           '127.0.0.1', '--master-port', str(port), osp.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4',
-                          '--warmup', '2'], capture_output=True, text=True, env=env, cwd=ROOT, timeout=880)
+                          '--warmup', '2', '--full'], capture_output=True, text=True, env=env, cwd=ROOT, timeout=880)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out.stdout[-2000:]                # rank 0 only
@@ -79,7 +103,7 @@ def test_bench_launches_its_own_ranks():
     the script execs the one-process-per-GPU launcher, and the command's stdout is still rank 0's ONE JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     env.update(PYTHONPATH=ROOT, GENESIS_BENCH_REHEARSAL='1', GENESIS_BENCH_LONG_STEPS='0')
-    out = subprocess.run([sys.executable, osp.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2'],
+    out = subprocess.run([sys.executable, osp.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--full'],
                          capture_output=True, text=True, env=env, cwd=ROOT, timeout=880)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]

@@ -1,5 +1,5 @@
 # A/B of library builds on the bench's timed loop:  tools/ab_bench.sh "<bench args>" <lib A> <lib B> ...   (each twice, interleaved)
 ARGS=$1; shift
 for rep in 1 2; do for L in "$@"; do
-  GENESIS_HIP_LIB=$GRAFT_REPO_ROOT/$L python bench.py $ARGS --steps 100 --warmup 20 --cpu-seconds 0 --fp32-pipe-steps 0 --host-input-steps 0 --extra-leg-steps 0 --profile-steps 0 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('%-34s %9.1f img/s  %.4f ms   steady %.1f' % ('$L', d['value'], d['ms_per_step'], d['steady_state']['value']))"
+  GENESIS_HIP_LIB=$PWD/$L python bench.py $ARGS --full --steps 100 --warmup 20 --cpu-seconds 0 --fp32-pipe-steps 0 --host-input-steps 0 --extra-leg-steps 0 --profile-steps 0 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('%-34s %9.1f img/s  %.4f ms   steady %.1f' % ('$L', d['value'], d['ms_per_step'], d['steady_state']['value']))"
 done; done

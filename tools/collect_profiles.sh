@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profiles_new
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/bench_default.log 2>&1
+python $R/bench.py --full > $OUT/bench_default.log 2>&1
 grep "^{" $OUT/bench_default.log > $OUT/bench_1gpu.json
-rocprofv3 --kernel-trace --stats -d /tmp/ks -o ks --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --fp32-pipe-steps 0 --host-input-steps 0 --extra-leg-steps 0 > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/ks -o ks --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --fp32-pipe-steps 0 --host-input-steps 0 --extra-leg-steps 0 > $OUT/bench_under_rocprof.log 2>&1
 cp /tmp/ks/*/ks_kernel_stats.csv $OUT/ 2>/dev/null || cp /tmp/ks/ks_kernel_stats.csv $OUT/
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pf -o f --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-graph --profile-steps 0 --cpu-seconds 0 --fp32-pipe-steps 0 --host-input-steps 0 --extra-leg-steps 0 > /tmp/pf.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d /tmp/pw -o w --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-graph --profile-steps 0 --cpu-seconds 0 --fp32-pipe-steps 0 --host-input-steps 0 --extra-leg-steps 0 > /tmp/pw.log 2>&1
