@@ -30,6 +30,114 @@ def u8hwc_to_f32chw(frames_u8, img_size=None, out=None):
     return out
 
 
+_RESAMPLE_MODES = {'nearest': 0, 'bilinear': 1}
+_LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
+_coeff_cache = {}
+
+
+def centre_box(Hs, Ws, crop):
+    """The centre-crop window (top, left, h, w) of an Hs x Ws frame, as utils/misc.py:45-56 np_img_centre_crop cuts it:
+    top = (Hs - h) // 2, left = (Ws - w) // 2.  `crop` is an int (square) or (h, w).  torchvision's CenterCrop (the PIL
+    path of datasets/shapestacks_config.py:126) uses round((Hs - h) / 2.0) instead, which differs only when Hs - h is odd
+    (floor vs round half to even); ShapeStacks (224 -> 196) and CLEVR (240 x 320 -> 192) have even differences."""
+    h, w = (crop, crop) if isinstance(crop, int) else (int(crop[0]), int(crop[1]))
+    if not (0 < h <= Hs and 0 < w <= Ws):
+        raise GenesisHipError('feeder: crop %dx%d does not fit a %dx%d frame' % (h, w, Hs, Ws))
+    return ((Hs - h) // 2, (Ws - w) // 2, h, w)
+
+
+def pil_bilinear_coeffs(n_in, n_out):
+    """Pillow's BILINEAR coefficient tables of one axis (host, C ABI gx_pil_bilinear_coeffs): bounds int32 [n_out, 2] =
+    (first source index, taps), weights int32 [n_out, ksize] with 22 fractional bits."""
+    import numpy as np
+    ksize = _lib.query('gx_pil_bilinear_ksize', int(n_in), int(n_out))
+    if ksize <= 0:
+        raise GenesisHipError('feeder: bad resample sizes %d -> %d' % (n_in, n_out))
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    weights = np.zeros((n_out, ksize), dtype=np.int32)
+    _lib.call('gx_pil_bilinear_coeffs', int(n_in), int(n_out), ksize, bounds.ctypes.data_as(ctypes.c_void_p),
+              weights.ctypes.data_as(ctypes.c_void_p))
+    return bounds, weights
+
+
+def _device_coeffs(Hc, H, Wc, W, device):
+    key = (Hc, H, Wc, W, device)
+    t = _coeff_cache.get(key)
+    if t is None:
+        hb, hw = pil_bilinear_coeffs(Wc, W)
+        vb, vw = pil_bilinear_coeffs(Hc, H)
+        t = tuple(torch.from_numpy(a).to(device) for a in (hb, hw, vb, vw))
+        _coeff_cache[key] = t
+    return t
+
+
+def _size_and_box(Hs, Ws, size, crop):
+    top, left, Hc, Wc = (0, 0, Hs, Ws) if crop is None else (int(v) for v in crop)
+    if size is None:
+        H, W = Hc, Wc
+    elif isinstance(size, int):
+        H = W = size
+    else:
+        H, W = int(size[0]), int(size[1])
+    return top, left, Hc, Wc, H, W
+
+
+def _check_out(out, shape, dtype, device):
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise GenesisHipError('feeder: out must be a contiguous %s tensor of shape %s on %s, not %s %s on %s'
+                              % (dtype, list(shape), device, out.dtype, list(out.shape), out.device))
+
+
+def transform_frames(frames_u8, size, crop=None, resize='nearest', out=None):
+    """frames_u8: uint8 device tensor [B, Hs, Ws, C] -> float32 [B, C, H, W], values / 255, of the crop window
+    crop = (top, left, h, w) (None: the whole frame) resampled to size = S or (H, W) (None: the window's size).
+    resize='nearest': F.interpolate's default mode (datasets/multi_object_config.py:181-202, CLEVR); 'bilinear': Pillow's
+    antialiased BILINEAR resize, which torchvision's Resize applies to a PIL image (datasets/shapestacks_config.py:126-130),
+    bit-exact."""
+    if not frames_u8.is_cuda:
+        raise GenesisHipError('feeder: frames must be on the HIP device; there is no CPU path')
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or not frames_u8.is_contiguous():
+        raise GenesisHipError('feeder: expected a contiguous uint8 [B,H,W,C] tensor')
+    if resize not in _RESAMPLE_MODES:
+        raise GenesisHipError('feeder: resize must be one of %s, not %r' % (sorted(_RESAMPLE_MODES), resize))
+    B, Hs, Ws, C = frames_u8.shape
+    top, left, Hc, Wc, H, W = _size_and_box(Hs, Ws, size, crop)
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=frames_u8.device)
+    _check_out(out, (B, C, H, W), torch.float32, frames_u8.device)
+    tables = [None] * 4
+    kh = kv = 0
+    if resize == 'bilinear' and min(Hc, Wc, H, W) > 0:
+        tables = [ctypes.c_void_p(t.data_ptr()) for t in _device_coeffs(Hc, H, Wc, W, frames_u8.device)]
+        kh, kv = _lib.query('gx_pil_bilinear_ksize', Wc, W), _lib.query('gx_pil_bilinear_ksize', Hc, H)
+    _lib.call('gx_u8hwc_resample_f32chw', ctypes.c_void_p(frames_u8.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, Hs, Ws,
+              C, top, left, Hc, Wc, H, W, _RESAMPLE_MODES[resize], tables[0], tables[1], kh, tables[2], tables[3], kv,
+              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def transform_labels(labels, size, crop=None, out=None):
+    """labels: uint8 / int32 / int64 device tensor [B, Hs, Ws] or [B, 1, Hs, Ws] -> int64 [B, 1, H, W]: the crop window
+    resampled nearest, as the reference moves instance maps (datasets/shapestacks_config.py:155-162,
+    multi_object_config.py:198-203: F.interpolate(cropped.float(), size).long()); equal to it for every label an fp32 holds
+    exactly.  crop / size as in transform_frames."""
+    if not labels.is_cuda:
+        raise GenesisHipError('feeder: labels must be on the HIP device; there is no CPU path')
+    if labels.dim() == 4 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if labels.dtype not in _LABEL_DTYPES or labels.dim() != 3 or not labels.is_contiguous():
+        raise GenesisHipError('feeder: expected a contiguous uint8 / int32 / int64 [B,H,W] label tensor')
+    B, Hs, Ws = labels.shape
+    top, left, Hc, Wc, H, W = _size_and_box(Hs, Ws, size, crop)
+    if out is None:
+        out = torch.empty(B, 1, H, W, dtype=torch.int64, device=labels.device)
+    _check_out(out, (B, 1, H, W), torch.int64, labels.device)
+    _lib.call('gx_labels_crop_nearest', ctypes.c_void_p(labels.data_ptr()), _LABEL_DTYPES[labels.dtype],
+              ctypes.c_void_p(out.data_ptr()), B, Hs, Ws, top, left, Hc, Wc, H, W,
+              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return out
+
+
 class DeviceFeeder(object):
     """Iterates fp32 device batches from an iterable of uint8 HWC host batches (numpy arrays or CPU tensors
     [B, H, W, C]).  A ring of `depth` slots (pinned staging buffer + uint8 device buffer); the host->device copy of
@@ -43,18 +151,30 @@ class DeviceFeeder(object):
     polling; nothing on the device waits compute -> copy.  Measured on MI355X / ROCm 7 under HIP-graph replay
     (tools/feeder_probe.py): a device-side compute -> copy event wait per batch costs 22 % img/s, and a host that blocks
     on an event fewer than ~30 batches old starves the graph-launch queue (depth 2: 1450 img/s, depth 8: 3700, against
-    6535 resident) -- hence the deep ring: at depth 32 the poll passes immediately in steady state (64x64: 26 MB)."""
+    6535 resident) -- hence the deep ring: at depth 32 the poll passes immediately in steady state (64x64: 26 MB).
 
-    def __init__(self, host_batches, img_size, device='cuda', depth=32):
+    Other datasets' transforms: `crop` = (top, left, h, w) (centre_box) and `resize` ('nearest' / 'bilinear') as in
+    transform_frames.  Dict batches {'input': uint8 [B,H,W,C], 'instances': int [B,H,W] or [B,1,H,W]} (as the reference's
+    loaders yield them; 'instances' optional) come out as {'input': fp32 [B,C,S,S], 'instances': int64 [B,1,S,S]}: a slot
+    then holds both buffers, and its `consumed` event is recorded after both conversions."""
+
+    def __init__(self, host_batches, img_size, device='cuda', depth=32, crop=None, resize='nearest'):
+        if resize not in _RESAMPLE_MODES:
+            raise GenesisHipError('feeder: resize must be one of %s, not %r' % (sorted(_RESAMPLE_MODES), resize))
         self.it = iter(host_batches)
         self.img_size = img_size
+        self.crop = crop
+        self.resize = resize
         self.device = torch.device(device)
         self.depth = max(2, int(depth))
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.pinned = [None] * self.depth
         self.dev_u8 = [None] * self.depth
+        self.pinned_lab = [None] * self.depth   # dict batches with 'instances': the label maps' staging / device buffers
+        self.dev_lab = [None] * self.depth
+        self.keys = [None] * self.depth      # keys of a dict batch in the slot; None: an array batch
         self.ready = [None] * self.depth     # copy-stream event: the H2D copy into dev_u8[s] has executed
-        self.consumed = [None] * self.depth  # consumer-stream event: the conversion kernel has read dev_u8[s]
+        self.consumed = [None] * self.depth  # consumer-stream event: the conversion kernels have read dev_u8[s] / dev_lab[s]
         self.filled = [False] * self.depth
         self.head = 0                        # slot the next __next__ consumes
         self.tail = 0                        # slot the next prefetch fills
@@ -71,12 +191,37 @@ class DeviceFeeder(object):
             nxt = next(self.it)
         except StopIteration:
             return
-        t = torch.as_tensor(nxt)
+        is_dict = isinstance(nxt, dict)
+        lab = None
+        if is_dict:
+            extra = set(nxt) - {'input', 'instances'}
+            if 'input' not in nxt or extra:
+                raise GenesisHipError("feeder: dict batches hold 'input' and optionally 'instances', not %s" % sorted(extra))
+            t = torch.as_tensor(nxt['input'])
+            if 'instances' in nxt:
+                lab = torch.as_tensor(nxt['instances'])
+                if lab.dim() == 4 and lab.shape[1] == 1:
+                    lab = lab[:, 0]
+                if lab.dtype not in _LABEL_DTYPES:
+                    if lab.dtype.is_floating_point or lab.dtype == torch.bool:
+                        raise GenesisHipError('feeder: instance maps must be integer, not %s' % lab.dtype)
+                    lab = lab.to(torch.int32)
+                if lab.dim() != 3 or t.dim() != 4 or lab.shape != t.shape[:3]:
+                    raise GenesisHipError('feeder: instances must be [B,H,W] or [B,1,H,W] of the input frames [B,H,W,C]')
+        else:
+            t = torch.as_tensor(nxt)
         if t.dtype != torch.uint8 or t.dim() != 4:
             raise GenesisHipError('feeder: host batches must be uint8 [B,H,W,C]')
         s = self.tail
         self._host_wait(self.ready[s])       # pinned[s] is free: its previous copy has executed
         self._host_wait(self.consumed[s])    # dev_u8[s] is free: the conversion kernel that read it has run
+        if lab is not None and (self.pinned_lab[s] is None or self.pinned_lab[s].shape != lab.shape
+                                or self.pinned_lab[s].dtype != lab.dtype):
+            for q in range(self.depth):      # the label ring likewise, all at once
+                if self.pinned_lab[q] is None or self.pinned_lab[q].shape != lab.shape or self.pinned_lab[q].dtype != lab.dtype:
+                    self._host_wait(self.ready[q]); self._host_wait(self.consumed[q])
+                    self.pinned_lab[q] = torch.empty(lab.shape, dtype=lab.dtype, pin_memory=True)
+                    self.dev_lab[q] = torch.empty(lab.shape, dtype=lab.dtype, device=self.device)
         if self.pinned[s] is None or self.pinned[s].shape != t.shape:
             # the whole ring at once, the first time a batch shape is seen: a pinned allocation costs ~1 ms of host time,
             # and 32 of them spread over the first 32 steps let the device queue run dry (the host needs the whole next
@@ -87,11 +232,16 @@ class DeviceFeeder(object):
                     self.pinned[q] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
                     self.dev_u8[q] = torch.empty(t.shape, dtype=torch.uint8, device=self.device)
         self.pinned[s].copy_(t)
+        if lab is not None:
+            self.pinned_lab[s].copy_(lab)
         with torch.cuda.stream(self.copy_stream):
             self.dev_u8[s].copy_(self.pinned[s], non_blocking=True)
+            if lab is not None:
+                self.dev_lab[s].copy_(self.pinned_lab[s], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self.ready[s] = ev
+        self.keys[s] = tuple(nxt) if is_dict else None
         self.filled[s] = True
         self.tail = (s + 1) % self.depth
 
@@ -104,7 +254,14 @@ class DeviceFeeder(object):
             raise StopIteration
         cur = torch.cuda.current_stream()
         cur.wait_event(self.ready[s])
-        x = u8hwc_to_f32chw(self.dev_u8[s], self.img_size)
+        if self.crop is None and self.resize == 'nearest':
+            x = u8hwc_to_f32chw(self.dev_u8[s], self.img_size)
+        else:
+            x = transform_frames(self.dev_u8[s], self.img_size, self.crop, self.resize)
+        if self.keys[s] is not None:
+            x = {'input': x}
+            if 'instances' in self.keys[s]:
+                x['instances'] = transform_labels(self.dev_lab[s], x['input'].shape[2:], self.crop)
         done = torch.cuda.Event()
         done.record(cur)
         self.consumed[s] = done

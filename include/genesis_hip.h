@@ -803,6 +803,38 @@ int gx_label_contingency(const long long* segA, const long long* segB, int B, in
 int gx_u8hwc_to_f32chw(const unsigned char* src, float* dst, int B, int Hs, int Ws, int C, int H, int W,
                        gx_stream_t stream);
 
+/* ---- feeder transforms of the other datasets (datasets/shapestacks_config.py:126-130 CenterCrop + PIL Resize + ToTensor,
+ *      :155-162 instance maps; datasets/multi_object_config.py:181-202 CLEVR centre crop + nearest F.interpolate):
+ *      gx_u8hwc_resample_f32chw: uint8 [B, Hs, Ws, C] -> fp32 [B, C, H, W] = value / 255 of the crop window (top, left, Hc, Wc)
+ *      resampled to H x W; the resample sees the window as the whole image.  mode GX_RESAMPLE_NEAREST: F.interpolate's
+ *      nearest rule (the full-frame window computes what gx_u8hwc_to_f32chw does; the tables may be null).
+ *      GX_RESAMPLE_PIL_BILINEAR: Pillow's 8-bit two-pass BILINEAR resampler (what torchvision's Resize does to a PIL image),
+ *      bit-exact; {h,v}bounds / {h,v}weights are DEVICE copies of gx_pil_bilinear_coeffs(Wc, W, ...) / (Hc, H, ...), with
+ *      ksize gx_pil_bilinear_ksize of the same sizes.  Any width and height; the downscale ratio r and channel count C are
+ *      bounded by the kernel's fixed LDS band buffers (16 KB intermediate + 32 KB staged source rows): about
+ *      (2r + 2)^2 x C source bytes must fit 32 KB, so up to r = 84 / 49 / 43 / 16 for C = 1 / 3 / 4 / 27 (at r = 16, at
+ *      most 27 channels); beyond that the call fails with GX_EINVAL ("exceeds the kernel's band buffers").  Bit-exact
+ *      against Pillow for 'L' (C = 1) and 'RGB' (C = 3) images and for opaque 'RGBA' (C = 4, alpha 255): Pillow
+ *      premultiplies RGBA by alpha around the resample, which this kernel does not do.
+ *      gx_pil_bilinear_ksize / gx_pil_bilinear_coeffs (host only, no GPU): Pillow's coefficient tables of one axis, computed in
+ *      double: bounds int32 [out][2] = (first source index, tap count), weights int32 [out][ksize] with 22 fractional bits.
+ *      gx_pil_bilinear_ksize returns 0 for a non-positive size.
+ *      gx_labels_crop_nearest: integer label maps [B, Hs, Ws] (dtype GX_LABEL_U8 / _I32 / _I64) -> int64 [B, 1, H, W],
+ *      nearest inside the crop window; equals the reference's F.interpolate(cropped.float()[:, None], size).long() for
+ *      every label an fp32 holds exactly (negative ignore labels included). */
+#define GX_RESAMPLE_NEAREST 0
+#define GX_RESAMPLE_PIL_BILINEAR 1
+#define GX_LABEL_U8 0
+#define GX_LABEL_I32 1
+#define GX_LABEL_I64 2
+int gx_pil_bilinear_ksize(int in, int out);
+int gx_pil_bilinear_coeffs(int in, int out, int ksize, int* bounds, int* weights);
+int gx_u8hwc_resample_f32chw(const unsigned char* src, float* dst, int B, int Hs, int Ws, int C, int top, int left, int Hc,
+                             int Wc, int H, int W, int mode, const int* hbounds, const int* hweights, int hksize,
+                             const int* vbounds, const int* vweights, int vksize, gx_stream_t stream);
+int gx_labels_crop_nearest(const void* src, int dtype, long long* dst, int B, int Hs, int Ws, int top, int left, int Hc, int Wc,
+                           int H, int W, gx_stream_t stream);
+
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
  *      bucket (parameters' gradients + the err / kl tail, genesis_amd/dp.py) is summed IN PLACE over the ranks by one
