@@ -797,6 +797,34 @@ int gx_gn_relu_fwd_parts(const float* parts, int nsplit, size_t split_stride, co
 int gx_label_contingency(const long long* segA, const long long* segB, int B, int HW, int KA, int KB, int* counts,
                          gx_stream_t stream);
 
+/* ---- FID on the device (scripts/compute_fid.py + third_party/pytorch_fid; genesis_amd/fid.py): pytorch_fid's FID Inception
+ *      (Inception-v3, BatchNorm folded into the conv weights by the caller) on NHWC fp32 activations, and the moments of its
+ *      features.  Every output's reduction order is fixed by the layer shape alone (no split-K, no atomics), so an image's
+ *      features are bit-identical whatever batch, batch size or position it is computed in.
+ *      gx_fid_preprocess: fp32 images [B, 3, H, W] in [0, 1] -> the network input [B, 299, 299, 3] (NHWC): quantise != 0
+ *      first restates the reference's PNG round trip per pixel, float32(uint8(clamp(255 x, 0, 255))) / 255 (the float32
+ *      product, truncated); then torch's CPU bilinear resize to 299 x 299 (align_corners=False) and 2x - 1.
+ *      gx_fid_conv_bias_relu: y = relu(conv(x, w) + bias) on the fp32 matrix pipe, x [B, H, W, Cin], any kh x kw, one
+ *      stride, padding (ph, pw); Ho = (H + 2 ph - kh) / stride + 1.  The output channels are N = n0 + n1 + n2 (sibling
+ *      convs of the same input stacked along N; n1 = n2 = 0 for one conv): channel n < n0 goes to channel d0_c0 + n of
+ *      d0 [B, Ho, Wo, d0_ctot], the next n1 to d1 from d1_c0, the last n2 to d2 from d2_c0.  w is the packed weight
+ *      [roundup(N, 64)][roundup(kh kw Cin, 16)], zero-padded, with k = (r kw + s) Cin + c; bias [N].
+ *      gx_fid_pool: x [B, H, W, C] -> channels [y_c0, y_c0 + C) of y [B, Ho, Wo, y_ctot] by mode: GX_FID_MAXPOOL_S2
+ *      (3 x 3, stride 2, no padding), GX_FID_MAXPOOL_S1P1 (3 x 3, stride 1, padding 1), GX_FID_AVGPOOL_S1P1 (3 x 3,
+ *      stride 1, padding 1, count_include_pad=False), GX_FID_GLOBAL_AVGPOOL (Ho = Wo = 1).
+ *      gx_fid_moments: adds sum_b f[b] into sum [D] and sum_b f[b] f[b]^T into sumsq [D, D] (fp64, images added one by one
+ *      in order: bit-reproducible and independent of how the images are split into batches); feats fp32 [B, D]. */
+#define GX_FID_MAXPOOL_S2 0
+#define GX_FID_MAXPOOL_S1P1 1
+#define GX_FID_AVGPOOL_S1P1 2
+#define GX_FID_GLOBAL_AVGPOOL 3
+int gx_fid_preprocess(const float* x, float* y, int B, int H, int W, int quantise, gx_stream_t stream);
+int gx_fid_conv_bias_relu(const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, int kh, int kw,
+                          int stride, int ph, int pw, float* d0, int d0_ctot, int d0_c0, int n0, float* d1, int d1_ctot,
+                          int d1_c0, int n1, float* d2, int d2_ctot, int d2_c0, int n2, gx_stream_t stream);
+int gx_fid_pool(const float* x, int B, int H, int W, int C, int mode, float* y, int y_ctot, int y_c0, gx_stream_t stream);
+int gx_fid_moments(const float* feats, int B, int D, double* sum, double* sumsq, gx_stream_t stream);
+
 /* ---- input feeder (datasets/multid_config.py:131-135 ToTensor + F.interpolate(size), multi_object_config.py:176-186):
  *      uint8 frames [B, Hs, Ws, C] (HWC, as stored) -> fp32 [B, C, H, W] = value / 255, nearest-neighbour resampled to
  *      H x W when the stored size differs (F.interpolate's default mode).  Bit-exact against the torch ops. */
