@@ -1643,17 +1643,18 @@ void launch_tapconv_inst(const float* in, const float* wp, const float* bias, fl
         return;
     }
     // LDS-DMA staging measured per mode (B=32, K=7): transposed conv fwd 32->64 481 -> 431 us, its dgrad 462 -> 454,
-    // conv3x3 1-2 % slower -> on for the 5x5 modes, off for conv3x3 (GENESIS_TAPCONV_DMA=0/1 forces all modes)
-    static const char* dma_env = getenv("GENESIS_TAPCONV_DMA");
-    const bool dma = dma_env ? dma_env[0] == '1' : MODE != M_C3;
+    // conv3x3 1-2 % slower -> on for the 5x5 modes (while the zero page is there), off for conv3x3
+    constexpr bool dma = MODE != M_C3;
     g.zeros = dma ? zero_page(s) : nullptr;
     if ((MODE == M_C3 || MODE == M_DG) && pl.mw == 2) {
         g.zeros = nullptr;
         launch_tapconv_inst2<MODE, NPOS, false, 2>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
         return;
     }
-    if (g.zeros) launch_tapconv_inst2<MODE, NPOS, true>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
-    else launch_tapconv_inst2<MODE, NPOS, false>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
+    if constexpr (dma) {
+        if (g.zeros) { launch_tapconv_inst2<MODE, NPOS, true>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s); return; }
+    }
+    launch_tapconv_inst2<MODE, NPOS, false>(in, wp, bias, out, g, pl.grid, pl.lds_bytes, s);
 }
 
 template <int NPOS, bool DMA, int MW = 1, bool STATS = false, bool B1 = false>
@@ -1791,12 +1792,10 @@ int launch_pack(const float* w, float* wp, int pack, int Co, int Ci, int NT, int
 
 // conv3x3 plan: 256-pixel tiles; grids that would have to split the channel reduction use 128-pixel tiles instead
 // (twice the workgroups, half the partial slabs or none).  Measured on all eight under-filled UNet layers (B=32):
-// 5-25 % faster each, 739 -> 690 us forward and 711 -> 660 us dgrad per step.  GENESIS_TAPCONV_MW2=0 disables.
+// 5-25 % faster each, 739 -> 690 us forward and 711 -> 660 us dgrad per step.
 int plan_c3(int N, int K, int M, int Mpad, int H, int W, TapPlan* pl, const char* name) {
     int rc = plan_tapconv<M_C3>(N, K, M, Mpad, H, W, H, W, H, W, 0, pl, name);
     if (rc || pl->g.nsplit == 1) return rc;
-    static const char* env = getenv("GENESIS_TAPCONV_MW2");
-    if (env && env[0] == '0') return rc;
     TapPlan p2;
     if (plan_tapconv<M_C3>(N, K, M, Mpad, H, W, H, W, H, W, 0, &p2, name, 1, 128) != GX_OK) return rc;
     *pl = p2;
@@ -1930,10 +1929,6 @@ void launch_wgrad_fast(dim3 grid, size_t lds_bytes, hipStream_t s, const float* 
 struct WfPending { WfJob job; size_t lds; double flops; };
 std::vector<WfPending> g_wf_ctx[kGxMaxCtx];
 #define g_wf (g_wf_ctx[gx_cur_ctx()])
-bool wf_defer_on() {
-    static const char* env = getenv("GENESIS_WGRAD_SMALL_DEFER");
-    return !(env && env[0] == '0');
-}
 
 template <int WM>
 int launch_wgrad(const float* a, const float* b, float* partial, const WgradPlan& pl, hipStream_t s, const char* name) {
@@ -1945,9 +1940,9 @@ int launch_wgrad(const float* a, const float* b, float* partial, const WgradPlan
         attr_set = true;
     }
     dim3 grid(pl.g.nsplit, (pl.g.CApad / 64) * (pl.g.CBpad / 64));
-    if (WM == W_C3 && pl.g.lTW == 2 && g_gx_defer_on && wf_defer_on() && (pl.g.Wb & 3) == 0 && pl.g.Hb * pl.g.Wb <= 65536 &&
+    if (WM == W_C3 && pl.g.lTW == 2 && g_gx_defer_on && (pl.g.Wb & 3) == 0 && pl.g.Hb * pl.g.Wb <= 65536 &&
         (double)(1 << pl.g.lG) * pl.g.CA * pl.g.Ha * pl.g.Wa < 2.0e9 && (double)(1 << pl.g.lG) * pl.g.CB * pl.g.Hb * pl.g.Wb < 2.0e9 &&
-        !getenv("GENESIS_WGRAD_LEGACY") && gx_defer_wgrad_room() > 0 && zero_page(s)) {
+        gx_defer_wgrad_room() > 0 && zero_page(s)) {
         // a layer too small for the stream-K launch: launched with the other queued ones at the flush (gx_wf_flush).
         // Only while the reduce queue has room for this layer's record (the caller pushes it next): with a full queue the
         // reduce runs at once, so the slabs must have been written by then -- the immediate launch below
@@ -1965,8 +1960,7 @@ int launch_wgrad(const float* a, const float* b, float* partial, const WgradPlan
         // lean kernel: 16-byte A loads (tile width >= 4 on a grid whose width is a multiple of 4), 31-bit offsets
         const bool fast = g.lTW >= 2 && g.lTW <= 5 && (g.Wb & 3) == 0 && g.Hb < 1024 && g.Wb < 1024 &&
                           (double)(1 << g.lG) * g.CA * g.Ha * g.Wa < 2.0e9 &&
-                          (double)(1 << g.lG) * g.CB * g.Hb * g.Wb < 2.0e9 && g.Hb * g.Wb <= 65536 &&
-                          !getenv("GENESIS_WGRAD_LEGACY");
+                          (double)(1 << g.lG) * g.CB * g.Hb * g.Wb < 2.0e9 && g.Hb * g.Wb <= 65536;
         const float* zeros = fast ? zero_page(s) : nullptr;
         if (fast && zeros) {
             switch (g.lTW) {
@@ -2113,13 +2107,11 @@ conv3x3_smallcin_fwd_kernel(const float* __restrict__ x, const float* __restrict
     }
 }
 static bool smallcin_fwd_ok(int Cin, int H, int W) {
-    static const char* env = getenv("GENESIS_CONV3_SMALLCIN_FWD");
-    // Cin == 4 only by default (MONet's [x | log-scope] input, modules/attention.py:36-40: 19.5 -> 12.2 us per pass).  The RGB
+    // Cin == 4 only (MONet's [x | log-scope] input, modules/attention.py:36-40: 19.5 -> 12.2 us per pass).  The RGB
     // layer of GENESIS-V2 gains as much (22.2 -> 14.3 us, + 0.3 % of its step) but another summation order in the network's first
     // layer moved ReLU decisions in the fp64-budget and full-batch-vs-chunks tests (DESIGN.md finding 18) beyond their measured
-    // allowances: GENESIS_CONV3_SMALLCIN_FWD=2 enables every Cin <= 4, =0 none
-    const bool all = env && env[0] == '2';
-    return !(env && env[0] == '0') && (Cin == 4 || (all && Cin >= 1 && Cin <= 4)) && (W % 4) == 0 && (long)H * W >= 1024;
+    // allowances
+    return Cin == 4 && (W % 4) == 0 && (long)H * W >= 1024;
 }
 
 // ---- conv3x3 weight gradient for very few input channels (Cin * 9 <= 32: the UNet's RGB input layer) -----------
@@ -2279,7 +2271,7 @@ bool c5_fast_plan(int N, int CA, int CB, int H, int W, WgradPlan* pl) {
     if (plan_wgrad(N, CA, CB, H, W, 1, 25, 1, pl, 128, 64, 2) != GX_OK) return false;
     const WgradGeom& g = pl->g;
     return g.lTW >= 2 && g.lTW <= 5 && pl->lds_bytes <= 160 * 1024 && (double)(1 << g.lG) * CA * H * W < 2.0e9 &&
-           (double)(1 << g.lG) * CB * H * W < 2.0e9 && !getenv("GENESIS_WGRAD_LEGACY");
+           (double)(1 << g.lG) * CB * H * W < 2.0e9;
 }
 template <int WM, int LTW>
 void launch_c5_fast(dim3 grid, size_t lds, hipStream_t s, const float* a, const float* b, float* partial, const float* zeros,
@@ -2557,9 +2549,7 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
         {
             GxProf pf(KID_TAPCONV_C3, s, 2.0 * N * (double)Cout * Cin * 9 * H * W,
                       4.0 * ((double)N * Cin * H * W + (double)N * Cout * H * W));
-#define GX_SC_LAUNCH(C_) hipLaunchKernelGGL(conv3x3_smallcin_fwd_kernel<C_>, grid, dim3(256), 0, s, x, w, bias, act, y, N, Cout, H, W)
-            if (Cin == 1) GX_SC_LAUNCH(1); else if (Cin == 2) GX_SC_LAUNCH(2); else if (Cin == 3) GX_SC_LAUNCH(3); else GX_SC_LAUNCH(4);
-#undef GX_SC_LAUNCH
+            hipLaunchKernelGGL(conv3x3_smallcin_fwd_kernel<4>, grid, dim3(256), 0, s, x, w, bias, act, y, N, Cout, H, W);
         }
         GX_CHECK_LAUNCH("gx_conv3x3_fwd(small Cin)");
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
@@ -2572,13 +2562,10 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
     float* part = wp + conv3x3_pack_floats(Cin, Cout);
     pl.g.act = act;
     const float* wpu;
-    static const char* kq_env = getenv("GENESIS_KQ");
-    const bool kq_first = kq_env && kq_env[0] == '2';        // benchmarking: the k-quad kernel ahead of Winograd
     const bool wino_ok = !bias && act == 0 && gx_wino_eligible(N, Cin, Cout, H, W);
     // <= 32 output channels: the bf16-pipe kernel with 32-channel workgroups, ahead of Winograd (whose 64-channel tile would be
-    // half empty: MONet's UNet 64 -> 32 layer 51 -> 38 us); GENESIS_KQ_C3H_FIRST=0: only where Winograd does not apply
-    static const char* c3h_first = getenv("GENESIS_KQ_C3H_FIRST");
-    if ((!wino_ok || !(c3h_first && c3h_first[0] == '0')) && gx_kq_c3h_eligible(N, Cin, Cout, H, W)) {
+    // half empty: MONet's UNet 64 -> 32 layer 51 -> 38 us)
+    if (gx_kq_c3h_eligible(N, Cin, Cout, H, W)) {
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 40: two fp16 pieces of w * 2^e (gx_kq_precision(2))
         const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 60: one bf16 piece (gx_kq_precision(3))
         rc = launch_pack(w, wp, 20 + f16 + b1, Cout, Cin, 9, gx_round_up(Cin, 16), Mpad, s, &wpu);
@@ -2591,7 +2578,7 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
-    if ((kq_first || !wino_ok) && gx_kq_c3_eligible(N, Cin, Cout, H, W)) {   // 16-byte operand reads (gx_kq.hip)
+    if (!wino_ok && gx_kq_c3_eligible(N, Cin, Cout, H, W)) {   // 16-byte operand reads (gx_kq.hip)
         rc = launch_pack(w, wp, 10, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
         if (rc) return rc;
         rc = gx_kq_c3_launch(x, wpu, bias, act, y, N, Cin, Cout, H, W, s);
@@ -2655,11 +2642,8 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
     float* wp = (float*)ws;
     float* part = wp + conv3x3_pack_floats(Cin, Cout);
     const float* wpu;
-    static const char* kq_env = getenv("GENESIS_KQ");
-    const bool kq_first = kq_env && kq_env[0] == '2';
     const bool wino_ok = gx_wino_eligible(N, Cout, Cin, H, W);
-    static const char* c3h_first = getenv("GENESIS_KQ_C3H_FIRST");
-    if ((!wino_ok || !(c3h_first && c3h_first[0] == '0')) && gx_kq_c3h_eligible(N, Cout, Cin, H, W)) {
+    if (gx_kq_c3h_eligible(N, Cout, Cin, H, W)) {
         const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 41
         const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 61
         rc = launch_pack(w, wp, 21 + f16 + b1, Cout, Cin, 9, gx_round_up(Cout, 16), Mpad, s, &wpu);
@@ -2669,7 +2653,7 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
         return gx_kq_c3h_launch(dy, wpu, nullptr, 0, dx, N, Cout, Cin, H, W, s, nullptr, 0, amax_ws,
                                 f16 ? (const float*)((const char*)wpu + gx_kq_h_amax_off(gx_round_up(Cout, 16), Mpad, 9)) : nullptr);
     }
-    if ((kq_first || !wino_ok) && gx_kq_c3_eligible(N, Cout, Cin, H, W)) {
+    if (!wino_ok && gx_kq_c3_eligible(N, Cout, Cin, H, W)) {
         rc = launch_pack(w, wp, 11, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
         if (rc) return rc;
         return gx_kq_c3_launch(dy, wpu, nullptr, 0, dx, N, Cout, Cin, H, W, s);
@@ -2697,8 +2681,6 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
  * epilogue of the bf16-pipe kernel (one more read of xout there instead of a pass that reads da and xout and writes dxa),
  * then the bias gradient as channel sums of dxa. */
 int gx_conv3x3_dgrad_act_supported(int N, int Cin, int Cout, int H, int W) {
-    static const char* env = getenv("GENESIS_DGRAD_ACT_FUSE");
-    if (env && env[0] == '0') return 0;
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
     return gx_kq_c3h_eligible(N, Cout, Cin, H, W) ? 1 : 0;
 }
@@ -2748,7 +2730,7 @@ int gx_conv3x3_wgrad(const float* x, const float* dy, float* dw, int N, int Cin,
     plan_wgrad(N, Cout, Cin, H, W, 1, 9, 1, &pl);
     GX_CHECK_ARG(ws_bytes >= gx_conv3x3_wgrad_ws_bytes(N, Cin, Cout, H, W), "gx_conv3x3_wgrad: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    if (smallcin_ok(Cin, H, W) && !getenv("GENESIS_WGRAD_LEGACY")) {
+    if (smallcin_ok(Cin, H, W)) {
         const int nblk = smallcin_blocks(N, H, W), mt = gx_ceil_div(Cout, 64);
         {
             GxProf pf(KID_WGRAD_C3, s, 2.0 * N * (double)Cout * Cin * 9 * H * W,
@@ -2782,8 +2764,7 @@ static bool wgrad_quad_plan(int N, int C, int H, int W, WgradPlan* pl) {
     if (plan_wgrad(N / 4, 64, 64, H, W, 1, 9, 1, pl, 64, 128) != GX_OK) return false;
     const WgradGeom& g = pl->g;
     if (g.lTW < 2 || g.lTW > 5 || pl->lds_bytes > 160 * 1024) return false;
-    if ((double)(1 << g.lG) * 128 * H * W >= 2.0e9 || (size_t)128 * H * W > kZeroFloats) return false;
-    return !getenv("GENESIS_WGRAD_LEGACY") && !getenv("GENESIS_WGRAD_NOQUAD");
+    return (double)(1 << g.lG) * 128 * H * W < 2.0e9 && (size_t)128 * H * W <= kZeroFloats;
 }
 int gx_conv3x3_wgrad_quad_supported(int N, int C, int H, int W) {
     WgradPlan pl;
@@ -2850,9 +2831,8 @@ static int wgrad_quad_impl(const float* x, const float* dy, float* dw, float* db
                                (float*)ws, zeros, g);                                                                    \
         }
         // tiles >= 8 pixels wide: on the bf16 matrix pipe (six piece products) unless gx_wgq_precision(0) /
-        // GENESIS_WGQ_BF16X6=0 / GENESIS_WGRAD_QUAD_B6=0 keep the weight gradients on the fp32 pipe
-        static const char* b6env = getenv("GENESIS_WGRAD_QUAD_B6");
-        const bool b6 = gx_wgq_bf16_pipe() && !(b6env && b6env[0] == '0');
+        // GENESIS_WGQ_BF16X6=0 keep the weight gradients on the fp32 pipe
+        const bool b6 = gx_wgq_bf16_pipe();
         bias_in_kernel = dbias && b6 && g.lTW >= 3;
         if (bias_in_kernel) g.bias_part = (float*)ws + pl.ws_floats;
         switch (g.lTW) {
@@ -3101,8 +3081,7 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
     TapPlan p0;
     rc = plan_tapconv<M_DT0>(N, Cin, Cout, Mpad, Hin, Win, Hin, Win, 2 * Hin, 2 * Win, 0, &p0, "gx_deconv5x5s2_fwd", 2);
     if (rc) return rc;
-    static const char* mw_env = getenv("GENESIS_TAPCONV_MW2");
-    if (p0.g.nsplit > 1 && !(mw_env && mw_env[0] == '0')) {   // 128-pixel tiles for under-filled grids (see plan_c3)
+    if (p0.g.nsplit > 1) {   // 128-pixel tiles for under-filled grids (see plan_c3)
         TapPlan p2;
         if (plan_tapconv<M_DT0>(N, Cin, Cout, Mpad, Hin, Win, Hin, Win, 2 * Hin, 2 * Win, 0, &p2, "gx_deconv5x5s2_fwd",
                                 2, 128) == GX_OK)
@@ -3124,8 +3103,7 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
         gx_tapconv_note(b1 ? 3 : 0);
         dim3 grid(p0.grid.x, p0.grid.y * 2, p0.grid.z);
         ConvGeom gg = p0.g;
-        static const char* dma_env = getenv("GENESIS_TAPCONV_DMA");
-        gg.zeros = (dma_env ? dma_env[0] == '1' : true) && !b1 ? zero_page(s) : nullptr;
+        gg.zeros = !b1 ? zero_page(s) : nullptr;
         if (b1) {             // one bf16 piece per operand: register staging (the input is converted on its way into LDS)
             const bool st_ok = stats && p0.mw == 1 && p0.npos == 2 && gg.nsplit == 1 && gg.lG == 0 && (Cout % 8) == 0;
             if (st_ok) {
@@ -3201,8 +3179,7 @@ int gx_deconv5x5s2_dgrad(const float* dy, const float* w, float* dx, int N, int 
     TapPlan pl;
     rc = plan_tapconv<M_DG>(N, Cout, Cin_out, Mpad, Hin, Win, 2 * Hin, 2 * Win, Hin, Win, 0, &pl, "gx_deconv5x5s2_dgrad");
     if (rc) return rc;
-    static const char* mw_env = getenv("GENESIS_TAPCONV_MW2");
-    if (pl.g.nsplit > 1 && !(mw_env && mw_env[0] == '0')) {
+    if (pl.g.nsplit > 1) {
         TapPlan p2;
         if (plan_tapconv<M_DG>(N, Cout, Cin_out, Mpad, Hin, Win, 2 * Hin, 2 * Win, Hin, Win, 0, &p2,
                                "gx_deconv5x5s2_dgrad", 1, 128) == GX_OK)

@@ -238,8 +238,6 @@ igemm_reduce_act_kernel(const float* __restrict__ partial, const float* __restri
 // splits of the forward conv's contraction: only where the output tiles leave most of the chip idle (the ComponentVAE encoder's
 // last stride-2 layers, modules/encoders.py:31-34, at K*B = 224 images: 64 -> 64 from 8 x 8 is 28 tiles of 36 K-chunks = 62 us)
 int fwd_splits(const IG& g) {
-    static const char* env = getenv("GENESIS_DCONV_FWD_SPLIT");
-    if (env && env[0] == '0') return 1;
     const int tiles = gx_ceil_div(g.Ncols, BN) * gx_ceil_div(g.M, BM), nchunks = gx_ceil_div(g.K, BK);
     if (tiles >= 128 || nchunks < 8) return 1;
     int ns = gx_ceil_div(256, tiles);
@@ -420,8 +418,6 @@ conv3x3s2_fwd_small_kernel(const float* __restrict__ x, const float* __restrict_
 
 // the launch above where it pays: conv3x3 stride 2 pad 1 on even grids, <= 64 input channels, a grid of >= 512 workgroups
 static bool fwd_small_ok(int N, int Cin, int Cout, int H, int W, int k, int stride, int pad) {
-    static const char* env = getenv("GENESIS_DCONV_FWD_SMALL");
-    if (env && env[0] == '0') return false;
     if (k != 3 || stride != 2 || pad != 1 || (H & 1) || (W & 1) || Cin > 64 || (double)N * H * W >= 2.0e9) return false;
     const long wgs = (long)gx_ceil_div(Cout, 8) * gx_ceil_div(N * (H / 2) * (W / 2), 256);
     return wgs >= 512 && gx_ceil_div(N * (H / 2) * (W / 2), 256) <= 65535;

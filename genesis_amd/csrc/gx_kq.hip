@@ -996,8 +996,6 @@ bool q_plan(int N, int K, int M, int Hb, int Wb, int Hi, int Wi, int Ho, int Wo,
     if ((double)N * K * Hi * Wi * 4.0 >= 2.0e9) return false;     // 31-bit byte offsets into the input tensor
     const int nw = (maxt * 128 + 255) / 256;
     *lds_bytes = ((size_t)2 * *nq * 1024 + (size_t)2 * nw * 1024) * sizeof(float);
-    static const char* pad_env = getenv("GENESIS_KQ_ONE_WG");     // measurement: one workgroup per CU
-    if (pad_env && pad_env[0] == '1' && *lds_bytes < 96 * 1024) *lds_bytes = 96 * 1024;
     return *lds_bytes <= 160 * 1024;
 }
 
@@ -1007,23 +1005,16 @@ bool q_plan(int N, int K, int M, int Hb, int Wb, int Hi, int Wi, int Ho, int Wo,
 // channels): 768 whole + 256 half workgroups = 3 + ~0.6 rounds.  Returns the number of whole-tile workgroups and sets
 // the grid width.  Only for full 64-channel tiles (M % 64 == 0 or > 32 in the last tile).
 int q_split_tail(int ptiles, int M, unsigned* grid_x) {
-    static const char* env = getenv("GENESIS_KQ_TAIL");
     const int r = ptiles % 256;
-    const bool split = !(env && env[0] == '0') && ptiles > 256 && r > 0 && r <= 128 && (M % 64 == 0 || M % 64 > 32);
+    const bool split = ptiles > 256 && r > 0 && r <= 128 && (M % 64 == 0 || M % 64 > 32);
     const int nfull = split ? ptiles - r : ptiles;
     *grid_x = (unsigned)(nfull + 2 * (ptiles - nfull));
     return nfull;
 }
 
-int g_kq_mode = -1;   // 0 off, 1 auto (layers whose grid fills the chip), 2 every eligible shape
+int g_kq_mode = 1;    // gx_kq_policy: 0 off, 1 auto (layers whose grid fills the chip), 2 every eligible shape
 
-int kq_mode() {
-    if (g_kq_mode < 0) {
-        const char* env = getenv("GENESIS_KQ");
-        g_kq_mode = env ? (env[0] == '0' ? 0 : (env[0] == '2' ? 2 : 1)) : 1;
-    }
-    return g_kq_mode;
-}
+int kq_mode() { return g_kq_mode; }
 
 bool q_fills(int N, int Hb, int Wb, int M, int mult) {
     const long wgs = (long)gx_ceil_div(N * Hb * Wb, 256) * gx_ceil_div(M, 64) * mult;
@@ -1167,7 +1158,7 @@ int gx_kq_weight_amax_launch(const float* w, int n, float* out, hipStream_t s) {
 // a producer that left THOUSANDS of partial maxima (one per workgroup of a gated unit's or a generic GroupNorm kernel's grid): one
 // small launch folds them into one value -- every workgroup of the conv reducing them all costs more (measured: kq_c5h 147 -> 160 us
 // per launch at 10 240 partials, kq_dgh 873 -> 911 us at 11 264) than this launch does (~4 us)
-static const int kFoldPartsAbove = [] { const char* e = getenv("GENESIS_KQ_FOLD_ABOVE"); return e ? atoi(e) : 1024; }();
+static const int kFoldPartsAbove = 1024;
 __global__ void __launch_bounds__(1024)
 amax_fold2_kernel(const float* __restrict__ p0, int n0, const float* __restrict__ p1, int n1, float* __restrict__ out) {
     __shared__ float red[16];
@@ -1223,8 +1214,6 @@ static size_t qh_lds(const QGeom& g, int nq, int np = 3) {
     const int CHS = (1 << g.lG) * ((1 << g.lTH) + 2) * ((1 << g.lTW) + 2);
     const size_t planes = nq == 4 ? (size_t)np * 2 * CHS * 16 : (size_t)np * nq * 256 * 16;
     const size_t lds = planes + (size_t)2 * NWH * 256 * 16;
-    static const char* env = getenv("GENESIS_KQ_H_NQ4");           // 0: shapes with four staging rounds stay on the fp32 pipe
-    if (nq == 4 && env && env[0] == '0') return 0;
     return lds <= 80 * 1024 ? lds : 0;
 }
 bool gx_kq_deconv_h_eligible(int N, int K, int M, int Hb, int Wb) {
@@ -1252,8 +1241,7 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
     else if (amax_ws) { const int rc = kq_fold_parts(&x_parts, &x_nparts, amax_ws, s); if (rc) return rc; }
     dim3 grid(1, gx_ceil_div(M, 64), 2);
     g.nfull = q_split_tail(g.tiles_h * g.tiles_w * gx_ceil_div(N, 1 << g.lG), M, &grid.x);
-    static const char* ilv_env = getenv("GENESIS_KQ_DTH_INTERLEAVE");       // 0: all 15-tap workgroups, then all 10-tap ones (grid.z)
-    if (!(ilv_env && ilv_env[0] == '0') && grid.y == 1) { g.ilv = 1; grid.x *= 2; grid.z = 1; }
+    if (grid.y == 1) { g.ilv = 1; grid.x *= 2; grid.z = 1; }       // 15-tap and 10-tap workgroups interleaved along x, not one after the other along z
     {
         GxProf pf(KID_KQ_DTH, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * Hb * Wb + (double)N * M * 4 * Hb * Wb + 25.0 * K * M));
@@ -1289,8 +1277,7 @@ static bool q_plan_c3h(int N, int K, int M, int H, int W, QGeom* g, int* nq, siz
     int TH = 1; while (TH * TW < 256 && H % (2 * TH) == 0) TH *= 2;
     int G = 256 / (TW * TH);
     g->rt_th = g->rt_tw = 0;
-    static const char* rt_env = getenv("GENESIS_KQ_C3H_ROWTILES");
-    if (!(rt_env && rt_env[0] == '0') && TW < W && TW < 32 && W <= 128 && 256 / W >= 2) {
+    if (TW < W && TW < 32 && W <= 128 && 256 / W >= 2) {
         // a width without a large power-of-two factor (the 72 x 72 canvas: 8): tiles of whole rows instead
         g->rt_tw = W; g->rt_th = 256 / W;
         TW = W; TH = g->rt_th; G = 1;
@@ -1308,8 +1295,7 @@ static bool q_plan_c3h(int N, int K, int M, int H, int W, QGeom* g, int* nq, siz
     return true;
 }
 bool gx_kq_c3h_eligible(int N, int K, int M, int H, int W) {
-    static const char* env = getenv("GENESIS_KQ_C3H");
-    if ((env && env[0] == '0') || !kq_h_on() || kq_mode() == 0 || M > 32) return false;
+    if (!kq_h_on() || kq_mode() == 0 || M > 32) return false;
     QGeom g; int nq; size_t lds;
     if (!q_plan_c3h(N, K, M, H, W, &g, &nq, &lds)) return false;
     return kq_mode() == 2 || (long)g.tiles_h * g.tiles_w * gx_ceil_div(N, 1 << g.lG) * gx_ceil_div(M, 32) >= 512;
@@ -1334,9 +1320,8 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
     }
     dim3 grid(g.tiles_h * g.tiles_w * gx_ceil_div(N, 1 << g.lG), gx_ceil_div(M, 32));
     g.nfull = (int)grid.x;                               // tiles; the workgroups loop over them (kq_c3h_kernel)
-    static const char* pers_env = getenv("GENESIS_KQ_C3H_PERSIST");
-    const int per_cu = pers_env ? atoi(pers_env) : 3;
-    if (per_cu > 0 && (int)grid.x > 256 * per_cu / (int)grid.y) grid.x = 256 * per_cu / grid.y;
+    const int per_cu = 3;                                // persistent workgroups per CU
+    if ((int)grid.x > 256 * per_cu / (int)grid.y) grid.x = 256 * per_cu / grid.y;
     // an armed gx_amax_tap: this launch writes every element of `out` -- one partial maximum per workgroup for the tensor's next
     // reader (the next layer of a BroadcastDecoder chain, forward or backward: no amax pass of its own over a 148 MB canvas)
     g.o_amax = amax_ws ? gx_amax_producer_out(out, false, grid.x * grid.y, (size_t)N * M * H * W) : nullptr;      // (the fp16 form only)
@@ -1380,12 +1365,10 @@ static bool q_plan_c5h(int N, int K, int M, int H, int W, QGeom* g, size_t* lds_
     return *lds_bytes <= 80 * 1024;
 }
 bool gx_kq_c5h_eligible(int N, int K, int M, int H, int W) {
-    static const char* env = getenv("GENESIS_KQ_C5H");
-    if ((env && env[0] == '0') || !kq_h_on() || kq_mode() == 0) return false;
+    if (!kq_h_on() || kq_mode() == 0) return false;
     QGeom g; size_t lds;
     if (!q_plan_c5h(N, K, M, H, W, &g, &lds)) return false;
-    static const int min_wgs = [] { const char* e = getenv("GENESIS_KQ_C5H_MIN_WGS"); return e ? atoi(e) : 192; }();
-    return kq_mode() == 2 || (long)g.nfull * gx_ceil_div(M, 64) >= min_wgs;
+    return kq_mode() == 2 || (long)g.nfull * gx_ceil_div(M, 64) >= 192;
 }
 int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K, int M, int H, int W, hipStream_t s,
                      float* amax_ws, const float* w_amax, const float* x_parts, int x_nparts) {

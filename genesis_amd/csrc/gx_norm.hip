@@ -1081,31 +1081,23 @@ template <int F, int UPW>
 bool launch_bwd_stage(dim3 grid, dim3 block, hipStream_t s, size_t lds, const float* y, const float* gamma,
                       const float* beta, const float* mean, const float* rstd, int C, int H, int W, int groups, int P,
                       View g0, View g1, float* dy, float* part, float* wpart, float* bpart) {
-    static const char* env = getenv("GENESIS_GN_STAGE2");
-    if (UPW != 1 || block.x != 1024 || g0.ctot != 4 || (env && env[0] == '0')) return false;
+    if (UPW != 1 || block.x != 1024 || g0.ctot != 4) return false;
     // an armed amax link (gx_kq_amax_link): one partial maximum of dy per workgroup for the conv that reads dy next
     float* amax_parts = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)(grid.x / groups) * C * H * W);
+    // slabs of F >= 8 float4 per thread re-read y in the second pass instead of spilling it; smaller ones keep it in registers
+    constexpr bool KEEP = F < 8;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, true, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, true, KEEP>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, false, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, true, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, false, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, false, KEEP>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         attr_set = true;
     }
-    // slabs of F >= 8 float4 per thread re-read y in the second pass instead of spilling it (GENESIS_GN_STAGE_KEEP=1: the
-    // register-resident form)
-    static const char* keep_env = getenv("GENESIS_GN_STAGE_KEEP");
-    const bool keep = F < 8 || (keep_env && keep_env[0] == '1');
-#define GX_STAGE_LAUNCH(WP_, KEEP_)                                                                                          \
-    hipLaunchKernelGGL((gn_relu_bwd_stage_kernel<F, 4, WP_, KEEP_>), grid, block, lds, s, y, gamma, beta, mean, rstd, C, H, W, \
+#define GX_STAGE_LAUNCH(WP_)                                                                                               \
+    hipLaunchKernelGGL((gn_relu_bwd_stage_kernel<F, 4, WP_, KEEP>), grid, block, lds, s, y, gamma, beta, mean, rstd, C, H, W, \
                        groups, P, g0, g1, dy, part, wpart, bpart, amax_parts)
-    if (wpart) { if (keep) GX_STAGE_LAUNCH(true, true); else GX_STAGE_LAUNCH(true, false); }
-    else { if (keep) GX_STAGE_LAUNCH(false, true); else GX_STAGE_LAUNCH(false, false); }
+    if (wpart) GX_STAGE_LAUNCH(true); else GX_STAGE_LAUNCH(false);
 #undef GX_STAGE_LAUNCH
     return true;
 }

@@ -959,8 +959,7 @@ static int conv1x1_bwd_impl(const float* x, const float* dy, const float* w, con
     GX_CHECK_LAUNCH("gx_conv1x1_bwd(dgrad)");
     {
         GxProf pf(KID_CONV1X1_WGRAD, s, 2.0 * N * Cin * Cout * HW, 4.0 * N * HW * (Cin + Cout));
-        static const bool legacy = getenv("GENESIS_CONV1X1_WGRAD_LEGACY") != nullptr;
-        if (Cin <= 64 && (HW % C1_TP) == 0 && !legacy) {
+        if (Cin <= 64 && (HW % C1_TP) == 0) {
             static bool attr_set = false;
             const size_t lds = (size_t)(64 + 8) * C1_LS * sizeof(float);
             if (!attr_set) {

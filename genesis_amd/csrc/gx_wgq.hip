@@ -1423,27 +1423,14 @@ bool wgq_b1() {
 }
 // units per fp16-piece tile by row-ring variant 18 .. 28 (0: the variant has no fp16 form), re-fitted with GENESIS_WGQ_TIMES on the
 // metric step next to the bf16 / LDS-DMA variants of the same launch: 64 - 78 % of the bf16 tile (the 10-tap row parity gains
-// least: its split / staging work per tile is that of the 15-tap one).  GENESIS_WGQ_F16_COST="c18,c19,c20,c21,c26,c27,c28" overrides
-int g_ws_cost_f16[16] = {3040, 1760, 2650, 2315,
+// least: its split / staging work per tile is that of the 15-tap one)
+const int g_ws_cost_f16[16] = {3040, 1760, 2650, 2315,
                          5300, 2700, 3560, 1850,      // ... of the 5 x 5 stride-1 conv (the gated stacks): 0.66 x the bf16 tile, estimates
                          1870, 2700, 2380,
                          3200, 2750, 2450,            // ... one strip per tile (the 128 x 128 model's large layers; fitted on the K = 11 step:
                                                       //     workgroups of the 10-tap parity ran 15 % over the others at 2150)
                          2700, 1850};                 // ... 5 x 5, two 16-pixel rows per tile: estimates
-bool g_ws_cost_f16_init = false;
-int ws_f16cost(int rv) {
-    if (!g_ws_cost_f16_init) {
-        g_ws_cost_f16_init = true;
-        if (const char* env = getenv("GENESIS_WGQ_F16_COST")) {
-            int v[7];
-            if (sscanf(env, "%d,%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6) == 7) {
-                static const int idx[7] = {0, 1, 2, 3, 8, 9, 10};
-                for (int i = 0; i < 7; ++i) if (v[i] > 0) g_ws_cost_f16[idx[i]] = v[i];
-            }
-        }
-    }
-    return g_ws_cost_f16[rv - 18];
-}
+int ws_f16cost(int rv) { return g_ws_cost_f16[rv - 18]; }
 bool ws_f16_variant(int rv) { return rv >= 18 && rv <= 33; }
 
 // which matrix pipe the weight gradients run on: 1 (default) bf16 pipe, fp32 products from six bf16 piece products
@@ -1495,14 +1482,8 @@ void wgq_launch(int cls, int ltw, const WqTable& tab, int total_wgs, const float
     }
 }
 
-int g_wgq_mode = -1;
-int wgq_mode() {
-    if (g_wgq_mode < 0) {
-        const char* env = getenv("GENESIS_WGQ");
-        g_wgq_mode = env ? (env[0] == '0' ? 0 : 1) : 1;
-    }
-    return g_wgq_mode;
-}
+int g_wgq_mode = 1;          // gx_wgq_policy: 0 off (the per-layer kernels of gx_conv.hip)
+int wgq_mode() { return g_wgq_mode; }
 
 // fills the geometry part of a job; false if the layer is not eligible
 bool wgq_make_job(int sa, const float* a, const float* b, float* partial, int N, int CA, int CB, int Hb, int Wb, int Ttot,
@@ -1557,20 +1538,14 @@ int wgq_launch_group(std::vector<PendingJob*>& grp, int budget, hipStream_t s) {
 
 
 // ---- stream-K host side ------------------------------------------------------------------------------------------
-int g_wgq_stream = -1;
-bool wgq_stream_on() {
-    if (g_wgq_stream < 0) {
-        const char* env = getenv("GENESIS_WGQ_STREAM");
-        g_wgq_stream = (env && env[0] == '0') ? 0 : 1;
-    }
-    return g_wgq_stream != 0;
-}
+int g_wgq_stream = 1;        // gx_wgq_policy(2): 0, one grouped launch per variant instead of the stream-K launch
+bool wgq_stream_on() { return g_wgq_stream != 0; }
 
 // units per tile of a variant (class * 3 + (5 - ltw)): ns per tile and workgroup of single-layer launches (tools/kq_time.py
 // wgrad3:256:64 wgrad3:2048:16 wgrad3:8192:8 wgrad:256:32 wgrad:1024:16 wgrad:4096:8: 10.3 us per conv3x3 tile, 26.5 us per
 // pair of transposed-conv row-parity tiles, split 15 a + b : 10 a + b), then nudged on the training step itself
-// (the stream kernel's duration over five vectors: 921 .. 972 us); GENESIS_WGQ_COST="c0,...,c8" overrides
-int g_ws_cost[34] = {10200, 9580, 9600, 15080, 21000, 11800, 11400, 8800, 9700,              // bf16 pipe (measured with
+// (the stream kernel's duration over five vectors: 921 .. 972 us)
+const int g_ws_cost[34] = {10200, 9580, 9600, 15080, 21000, 11800, 11400, 8800, 9700,              // bf16 pipe (measured with
                      10200, 10600, 11200, 16000, 16500, 18200, 11600, 12000, 13300,           // GENESIS_WGQ_TIMES) | fp32 pipe
                      4840, 2450, 4150, 2900,                                                  // row-ring tiles (one base row)
                      8000, 4100, 5400, 2800,                                                  // ... of the 5 x 5 stride-1 conv
@@ -1579,33 +1554,8 @@ int g_ws_cost[34] = {10200, 9580, 9600, 15080, 21000, 11800, 11400, 8800, 9700, 
                      4100, 2800};                                                             // ... 5 x 5, two 16-pixel rows per tile
 // cost of a k-split tile relative to the full one, in percent, by base variant 18..25 (one or the other half) and for both
 // halves of variant 18 (measured with GENESIS_WGQ_TIMES on the GENESIS / BaselineVAE / MONet steps: the 32-pixel rows keep one
-// k-group per wave -- their tile starts with the operand reads the tail could not take); GENESIS_WGQ_KSPLIT_COST="9 values" overrides
-int g_ws_kcost[9] = {54, 68, 68, 78, 54, 58, 55, 65, 41};
-bool g_ws_cost_init = false;
-void ws_cost_init() {
-    if (g_ws_cost_init) return;
-    g_ws_cost_init = true;
-    const char* env = getenv("GENESIS_WGQ_COST");
-    if (const char* er = getenv("GENESIS_WGQ_RING_COST")) {
-        int r[4];
-        if (sscanf(er, "%d,%d,%d,%d", r, r + 1, r + 2, r + 3) == 4)
-            for (int i = 0; i < 4; ++i) if (r[i] > 0) g_ws_cost[18 + i] = r[i];
-    }
-    if (const char* er = getenv("GENESIS_WGQ_R2_COST")) {       // two-rows-per-tile variants: conv3x3, transposed-conv rows 0 / 1
-        int r[3];
-        if (sscanf(er, "%d,%d,%d", r, r + 1, r + 2) == 3)
-            for (int i = 0; i < 3; ++i) if (r[i] > 0) g_ws_cost[26 + i] = r[i];
-    }
-    if (const char* er = getenv("GENESIS_WGQ_KSPLIT_COST")) {
-        int r[9];
-        if (sscanf(er, "%d,%d,%d,%d,%d,%d,%d,%d,%d", r, r + 1, r + 2, r + 3, r + 4, r + 5, r + 6, r + 7, r + 8) == 9)
-            for (int i = 0; i < 9; ++i) if (r[i] > 0) g_ws_kcost[i] = r[i];
-    }
-    if (!env) return;
-    int v[9];          // the nine costs of the pipe in use
-    if (sscanf(env, "%d,%d,%d,%d,%d,%d,%d,%d,%d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8) == 9)
-        for (int i = 0; i < 9; ++i) if (v[i] > 0) g_ws_cost[(wgq_b6() ? 0 : 9) + i] = v[i];
-}
+// k-group per wave -- their tile starts with the operand reads the tail could not take)
+const int g_ws_kcost[9] = {54, 68, 68, 78, 54, 58, 55, 65, 41};
 // units per one-piece tile: a FIRST FIT, not a measurement -- per variant, the line through the measured costs of its six-product
 // (g_ws_cost) and three-product (g_ws_cost_f16) tiles, cost = a + b * products, taken at one product, and never below a quarter of
 // the six-product tile (the staging / prologue share the line leaves); the LDS-DMA tiles (0 .. 8, no fp16 form): half their cost.
@@ -1618,35 +1568,25 @@ int ws_b1cost(int v) {
     return c > b6 / 4 ? c : b6 / 4;
 }
 
-// row-ring tiles (wr_segment): on the bf16 pipe, for full-width rows of 32 / 64 pixels; GENESIS_WGQ_RING=0 / gx_wgq_ring(0)
-// keep every layer on the 64-pixel LDS-DMA tiles (the A/B reference)
-int g_wgq_ring = -1;
-bool wgq_ring_on() {
-    if (g_wgq_ring < 0) {
-        const char* env = getenv("GENESIS_WGQ_RING");
-        g_wgq_ring = (env && env[0] == '0') ? 0 : 1;
-    }
-    return g_wgq_ring != 0;
-}
+// row-ring tiles (wr_segment): on the bf16 pipe, for full-width rows of 32 / 64 pixels; gx_wgq_ring(0) keeps every layer
+// on the 64-pixel LDS-DMA tiles (the A/B reference)
+int g_wgq_ring = 1;
+bool wgq_ring_on() { return g_wgq_ring != 0; }
 int ws_ring_variant(int cls, int Hb, int Wb) {
     if (!wgq_b6() || !wgq_ring_on() || Hb < 4) return -1;          // (H a multiple of 4: the ring slot of a row is tile & 3)
-    static const char* r2env = getenv("GENESIS_WGQ_RING16");       // 0: 16-pixel rows stay on the 64-pixel LDS-DMA tiles
-    if (Wb == 16 && !(r2env && r2env[0] == '0') && Hb >= 8 && Hb % 8 == 0 && cls <= WQ_DR1) return 26 + cls;   // two image rows per tile
-    if (Wb == 16 && !(r2env && r2env[0] == '0') && Hb >= 8 && Hb % 8 == 0 && (cls == WQ_C5A || cls == WQ_C5B)) return cls == WQ_C5A ? 32 : 33;
-    // rows too wide for the ring as two strips (the 128 x 128 model's large layers); GENESIS_WGQ_STRIPS=0: on the 64-pixel tiles
-    static const char* stenv = getenv("GENESIS_WGQ_STRIPS");
-    const bool strips = !(stenv && stenv[0] == '0');
-    if (cls == WQ_C3) return Wb == 64 ? 18 : (Wb == 32 ? 19 : (Wb == 128 && strips ? 29 : -1));
+    if (Wb == 16 && Hb >= 8 && Hb % 8 == 0 && cls <= WQ_DR1) return 26 + cls;   // two image rows per tile
+    if (Wb == 16 && Hb >= 8 && Hb % 8 == 0 && (cls == WQ_C5A || cls == WQ_C5B)) return cls == WQ_C5A ? 32 : 33;
+    // rows too wide for the ring as two strips (the 128 x 128 model's large layers)
+    if (cls == WQ_C3) return Wb == 64 ? 18 : (Wb == 32 ? 19 : (Wb == 128 ? 29 : -1));
     if (cls == WQ_C5A || cls == WQ_C5B) return Wb == 64 ? (cls == WQ_C5A ? 22 : 24) : (Wb == 32 ? (cls == WQ_C5A ? 23 : 25) : -1);
-    if (Wb == 64 && strips) return cls == WQ_DR0 ? 30 : 31;
+    if (Wb == 64) return cls == WQ_DR0 ? 30 : 31;
     if (Wb != 32) return -1;
     return cls == WQ_DR0 ? 20 : 21;
 }
 
-// k-split form of a row-ring variant for a channel block with ca_n x cb_n channels (0: none).  GENESIS_WGQ_KSPLIT=0: off
+// k-split form of a row-ring variant for a channel block with ca_n x cb_n channels (0: none)
 int ws_ksplit(int rv, int ca_n, int cb_n) {
-    static const char* env = getenv("GENESIS_WGQ_KSPLIT");
-    if ((env && env[0] == '0') || rv < 18 || rv > 25) return 0;
+    if (rv < 18 || rv > 25) return 0;
     int hf = (ca_n <= 32 ? 1 : 0) | (cb_n <= 32 ? 2 : 0);
     if (hf == 3 && rv != 18) hf = 1;          // (both halves empty: built for the 64-pixel conv3x3 rows only)
     return hf;
@@ -1684,7 +1624,6 @@ bool ws_plan(WsTable& tab, std::vector<WsSlot>& slots, int G) {
 int wgq_launch_stream(std::vector<PendingJob*>& jobs, hipStream_t s, std::vector<GxWgradRed>& recs) {
     const float* zeros = zero16(s);
     if (!zeros) { gx_set_error("wgq: zero page unavailable (first call inside a stream capture)"); return GX_ELAUNCH; }
-    ws_cost_init();
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgq_stream_kernel),

@@ -833,24 +833,19 @@ static bool wino_shape_ok(int N, int K, int M, int H, int W) {
 }
 
 // used by gx_conv3x3_fwd / _dgrad: Winograd where the shape allows it AND the grid fills the chip without a channel
-// split (under-filled layers stay on the direct kernels, which split the reduction).  GENESIS_WINOGRAD=0 disables.
-static int g_wino_mode = -1;   // 0 off, 1 auto (chip-filling layers), 2 every eligible shape; -1: not yet read from the env
+// split (under-filled layers stay on the direct kernels, which split the reduction).
+static int g_wino_mode = 1;    // gx_conv3x3_wino_policy: 0 off, 1 auto (chip-filling layers), 2 every eligible shape
 
 bool gx_wino_eligible(int N, int K, int M, int H, int W) {
-    if (g_wino_mode < 0) {
-        const char* env = getenv("GENESIS_WINOGRAD");
-        g_wino_mode = env ? (env[0] == '0' ? 0 : (env[0] == '2' ? 2 : 1)) : 1;
-    }
     if (g_wino_mode == 0 || !wino_shape_ok(N, K, M, H, W)) return false;
     // a quarter-filled chip is enough where the direct kernel has next to no reduction to split (<= 32 input channels; measured
     // per layer at 16 x 16, N = 32 with tools/conv3_policy_time.py: 32 -> 64 20.0 -> 17.0 us, the data gradient of 128 -> 32
     // 25.8 -> 17.9 us; 256 -> 64 is 41.3 -> 48.9 and stays direct).  Wider layers would gain 3 - 10 us as well (64 -> 128: 29.5 ->
     // 19.7), but they are GENESIS-V2's, whose B = 32 step is pinned against its own chunks of two images
     // (test_full_batch_equals_sixteen_golden_sized_chunks): a layer that changes kernels with the batch size moves ReLU decisions
-    // (DESIGN.md finding 18) for 0.4 % of the step.  GENESIS_WINO_SMALL=0: the chip-filling rule alone
-    static const char* small_env = getenv("GENESIS_WINO_SMALL");
+    // (DESIGN.md finding 18) for 0.4 % of the step.
     const int wgs = N * (H / 8) * (W / 16) * gx_ceil_div(M, 64);
-    return g_wino_mode == 2 || wgs >= 256 || (wgs >= 64 && K <= 32 && N >= 16 && !(small_env && small_env[0] == '0'));
+    return g_wino_mode == 2 || wgs >= 256 || (wgs >= 64 && K <= 32 && N >= 16);
 }
 
 // in2 / K1, out2 / M1: the pair variants (WinoGeom); nullptr / 0 for one input tensor and one output tensor
@@ -872,14 +867,11 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
     if (!out2) out2 = out;
     // bf16 pipe: 32-tile workgroups, two per CU.  The 64-tile variant (one workgroup per CU, half the A-operand traffic per
     // MFMA, A prefetch two positions deep) was measured SLOWER -- 51.1 vs 48.6 us (64 -> 64 @ 64 x 64, B = 32), 94.6 vs 83.2 us
-    // (128 -> 64): one wave per SIMD has nobody to hand the matrix pipe to while it waits -- and is kept behind
-    // GENESIS_WINO_NB=2 for measurement only.
-    static const char* nb_env = getenv("GENESIS_WINO_NB");
-    const int nb = (h && !f16 && !b1 && (H % 16) == 0 && nb_env && nb_env[0] == '2') ? 2 : 1;
-    g.tiles_h = H / (2 * WTH * nb);
+    // (128 -> 64): one wave per SIMD has nobody to hand the matrix pipe to while it waits -- and is no longer instantiated.
+    g.tiles_h = H / (2 * WTH);
     g.tiles_w = W / (2 * WTW);
     static bool attr_set = false;
-    const size_t lds = h ? (nb == 2 ? WHCfg<2>::LDS_BYTES : WHCfg<1>::LDS_BYTES)
+    const size_t lds = h ? WHCfg<1>::LDS_BYTES
                          : (size_t)(2 * RAW_FLOATS + 2 * V_FLOATS) * sizeof(float);
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_kernel),
@@ -890,19 +882,14 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<1, WPF_B1>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_conv_h_kernel<2, WPF_B6>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
     {
         const double flops = 2.0 * N * (double)M * K * 9 * H * W;    // algorithmic (direct-sum) flops
-        if (h) { g_wino_flops_all += flops; if (f16 && nb == 1) g_wino_flops_f16 += flops; }
+        if (h) { g_wino_flops_all += flops; if (f16) g_wino_flops_f16 += flops; }
         const double bytes = 4.0 * ((double)N * K * H * W + (double)N * M * H * W + 9.0 * K * M);
         GxProf pf(KID_WINO, s, flops, bytes);
-        if (h && nb == 2)
-            hipLaunchKernelGGL((wino_conv_h_kernel<2, WPF_B6>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
-                               reinterpret_cast<const unsigned*>(U), out, out2, g);
-        else if (h && b1)
+        if (h && b1)
             hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B1>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else if (h && f16)

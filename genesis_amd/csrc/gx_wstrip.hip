@@ -342,8 +342,6 @@ bool strip_geom(int N, int C, int H, int W, StripGeom* g) {
 }  // namespace
 
 bool gx_wstrip_supported(int N, int C, int H, int W) {
-    static const char* env = getenv("GENESIS_WGRAD_STRIP");
-    if (env && env[0] == '0') return false;
     StripGeom g;
     return gx_wgq_bf16_pipe() && strip_geom(N, C, H, W, &g);
 }

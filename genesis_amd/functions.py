@@ -31,13 +31,12 @@ class _StepState(object):
     TrainSteps in one process never see each other's flags, queues or keep-alive lists.  Autograd runs a HIP node's
     backward on its device thread: every Function below records the context of its forward and makes it current again
     at the start of its backward (ctx_bound), so forward and backward of one step always share one state."""
-    __slots__ = ('direct_param_grads', 'direct_written', 'async_wgrad', 'side_prior', 'side_stream', 'keep_alive', 'early_flush')
+    __slots__ = ('direct_param_grads', 'direct_written', 'async_wgrad', 'side_stream', 'keep_alive', 'early_flush')
 
     def __init__(self):
         self.direct_param_grads = False
         self.direct_written = set()    # ids of parameters whose .grad was already written directly this iteration
         self.async_wgrad = False
-        self.side_prior = False
         self.side_stream = None
         self.keep_alive = []
         self.early_flush = None        # callable: the decoder's backward is complete (TrainStep, GENESIS_WGQ_EARLY_FLUSH=1)
@@ -140,7 +139,6 @@ def _gout(p, acc=False):
 # optimiser.  Temporaries they read are kept alive until the join (no allocator reuse hazard across streams).
 # MEASURED (round 1, B=32 K=7 64x64): 4066 -> 3464 img/s with the fork on -- the 131 KB-LDS wgrad workgroups and
 # the 62 KB tap-conv workgroups evict each other from the CUs and both are MFMA-bound -- so TrainStep leaves it OFF.
-ASYNC_WGRAD_MAX_PIXELS = int(__import__('os').environ.get('GENESIS_ASYNC_WGRAD_MAX_PIXELS', 1 << 62))
 def _side():
     st = step_state()
     if st.side_stream is None:
@@ -150,9 +148,7 @@ def _side():
 
 def _wgrad(fn_, out, *reads):
     """Runs fn_() (a weight-gradient launch writing into `out`) on the side stream when allowed, else inline."""
-    # only layers whose kernels cannot fill the chip are forked (ASYNC_WGRAD_MAX_PIXELS images*H*W of the layer input)
-    if step_state().async_wgrad and out is not None and reads and \
-            reads[0].shape[0] * reads[0].shape[2] * reads[0].shape[3] <= ASYNC_WGRAD_MAX_PIXELS:
+    if step_state().async_wgrad and out is not None and reads:
         side = _side()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -168,39 +164,6 @@ def join_side_stream():
     if st.side_stream is not None:
         torch.cuda.current_stream().wait_stream(st.side_stream)
     st.keep_alive.clear()
-
-
-# ---- the AR-prior branch on the side stream ----------------------------------------------------------------
-# z -> LSTM -> linear -> log p(z) -> KL is a chain of ~12 launch-latency-bound kernels (32 workgroups each) that
-# depends only on the posterior sample and joins the main path again at the loss; forward and backward (autograd runs
-# a node's backward on its forward's stream) it can run in the shadow of the decoder's chip-filling kernels.  Inside
-# the captured step it becomes a parallel branch of the HIP graph.
-# MEASURED (round 1, B=32 K=7 64x64, A/B in one session): 5710 img/s without, 5640 with the fork -- the graph's
-# fork/join synchronisation costs more than the ~150 us of tiny kernels it hides -- so TrainStep leaves it OFF
-# (GENESIS_SIDE_PRIOR=1 / TrainStep(side_prior=True) turns it on).
-
-
-class side_branch(object):
-    """with side_branch(*tensors_read_inside): ...   -- forks the body onto the side stream; join_branch() before the
-    results are consumed on the main stream.  Tensors read inside are kept alive until join_side_stream()."""
-
-    def __init__(self, *reads):
-        self.reads = reads
-
-    def __enter__(self):
-        side = _side()
-        side.wait_stream(torch.cuda.current_stream())
-        step_state().keep_alive.extend(self.reads)
-        self.ctx = torch.cuda.stream(side)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        return self.ctx.__exit__(*exc)
-
-
-def join_branch():
-    torch.cuda.current_stream().wait_stream(_side())
 
 
 def _decoder_backward_done():
@@ -449,13 +412,10 @@ class ICSBPFn(torch.autograd.Function):
 
 
 # seg_head's GroupNorm+ReLU output is consumed by the colour head's 1x1 conv only: keep it out of memory (as the
-# decoder head; GENESIS_FUSE_SEG_HEAD=0 restores ConvGNReLUFn + ICSBPFn)
-FUSE_SEG_HEAD = __import__('os').environ.get('GENESIS_FUSE_SEG_HEAD', '1') == '1'
-
-
+# decoder head; shapes the fused kernels refuse take ConvGNReLUFn + ICSBPFn)
 def seg_head_fusable(enc_feat, seg_w, conv_w):
     C, HW = seg_w.shape[0], enc_feat.shape[2] * enc_feat.shape[3]
-    return FUSE_SEG_HEAD and C <= 64 and C % GROUPS == 0 and HW % 256 == 0 and conv_w.shape[0] <= 8
+    return C <= 64 and C % GROUPS == 0 and HW % 256 == 0 and conv_w.shape[0] <= 8
 
 
 @ctx_bound
@@ -514,11 +474,8 @@ class SegICSBPFn(torch.autograd.Function):
                 _ret(og, dgate), None, _ret(ols, dls.to(ctx.ls_dtype)), None, None, None, None, None)
 
 
-PAIR_HEADS = __import__('os').environ.get('GENESIS_PAIR_HEADS', '1') == '1'
-
-
 def heads_pairable(enc_feat, seg_w, conv_w, feat_w):
-    return PAIR_HEADS and seg_head_fusable(enc_feat, seg_w, conv_w) and feat_w.shape[1:] == seg_w.shape[1:] \
+    return seg_head_fusable(enc_feat, seg_w, conv_w) and feat_w.shape[1:] == seg_w.shape[1:] \
         and hip.conv3x3_pair_supported(enc_feat, seg_w, feat_w)
 
 
@@ -614,15 +571,9 @@ class MaskPoolFn(torch.autograd.Function):
         return df, dlog_m
 
 
-# last decoder stage without its normalised activation in memory (GENESIS_FUSE_DEC_HEAD=0: the unfused kernels)
-FUSE_DECODER_HEAD = __import__('os').environ.get('GENESIS_FUSE_DEC_HEAD', '1') == '1'
-# its GroupNorm statistics out of the transposed conv's epilogue instead of a statistics-only pass over the output
-EPILOGUE_STATS = __import__('os').environ.get('GENESIS_DECONV_STATS', '1') == '1'
-# first decoder layer on the broadcast latent as one matrix product over tap-summed weights instead of a transposed conv on
-# a materialised canvas (GENESIS_BCAST_DECONV=0: canvas + the generic kernels)
-BCAST_DECONV = __import__('os').environ.get('GENESIS_BCAST_DECONV', '1') == '1'
-
-
+# DecoderFn, where the shapes allow: the last stage without its normalised activation in memory, its GroupNorm statistics
+# out of the transposed conv's epilogue; the first layer on the broadcast latent as one matrix product over tap-summed
+# weights instead of a transposed conv on a materialised canvas.  Other shapes take the unfused / generic kernels.
 @ctx_bound
 class DecoderFn(torch.autograd.Function):
     """args: z [K*B, D], coords [1,2,d,d], then 4 x (deconv w, deconv b, gn gamma, gn beta), out w, out b."""
@@ -632,7 +583,7 @@ class DecoderFn(torch.autograd.Function):
         N, D = z.shape
         d = coords.shape[-1]
         z = z.contiguous()
-        ctx.bcast = BCAST_DECONV and params[0].shape[0] == D + 2
+        ctx.bcast = params[0].shape[0] == D + 2
         h = None
         if not ctx.bcast:
             h = hip.broadcast_concat(z, coords)      # BroadcastLayer + PixelCoords: one launch, no torch.cat
@@ -642,7 +593,7 @@ class DecoderFn(torch.autograd.Function):
         # last stage: the normalised 64-channel full-resolution activation (the largest tensor of the model) is never
         # written -- the output conv normalises the pre-norm tensor on load, forward and backward
         Cl, Sl = params[12].shape[1], 16 * d
-        ctx.fused_head = FUSE_DECODER_HEAD and Cl <= 64 and Cl % GROUPS == 0 and (Sl * Sl) % 256 == 0 \
+        ctx.fused_head = Cl <= 64 and Cl % GROUPS == 0 and (Sl * Sl) % 256 == 0 \
             and ow.shape[0] <= 8
         am_h = None           # partial maxima of the current layer's input (hip_ops.Amax), for the fp16-piece weight gradients
         ctx.am_h = [None] * 4
@@ -650,10 +601,7 @@ class DecoderFn(torch.autograd.Function):
             ctx.am_h[l] = am_h
             w, b, gamma, beta = params[4 * l:4 * l + 4]
             if l == 3 and ctx.fused_head:
-                if EPILOGUE_STATS:
-                    y, mean, rstd = hip.deconv5x5s2_gn_stats_fwd(h, w, b, gamma, beta, GROUPS, EPS)
-                else:
-                    y, mean, rstd = hip.deconv5x5s2_gn_relu_fwd(h, w, b, gamma, beta, GROUPS, EPS, None)
+                y, mean, rstd = hip.deconv5x5s2_gn_stats_fwd(h, w, b, gamma, beta, GROUPS, EPS)
                 saved.append((h, y, mean, rstd))
                 out = hip.conv1x1_gn_fwd(y, mean, rstd, gamma, beta, GROUPS, ow2, ob)
                 h = None
@@ -719,7 +667,7 @@ class DecoderFn(torch.autograd.Function):
                 am_dy = am_head
             else:
                 ow, obias, og, ob = _gout(w), _gout(b), _gout(gamma), _gout(beta)
-                link = hip.amax_link(da.device, y.numel()) if l > 0 and hip.AMAX_LINK_REG else None     # dy's partial maxima for this layer's data gradient; noqa: F841
+                link = hip.amax_link(da.device, y.numel()) if l > 0 else None     # dy's partial maxima for this layer's data gradient; noqa: F841
                 dy, dgamma, dbeta, dbias = hip.gn_relu_bwd(y, gamma, beta, mean, rstd, GROUPS, (da, 0, 0), None, True,
                                                            out=(og, ob, obias))
                 am_dy = hip.take_amax()
@@ -947,11 +895,11 @@ class BroadcastDecoderFn(torch.autograd.Function):
         for l in range(nl):
             w, b = params[2 * l], params[2 * l + 1]
             if l == 0:
-                tap = CHAIN_TAPS and nl > 1
+                tap = nl > 1
                 y = hip.bcast_conv3x3_fwd(z, w, b, rowc, colc, act, tap=tap)
                 am = hip.take_amax() if tap else None
             else:
-                tap = CHAIN_TAPS and l + 1 < nl
+                tap = l + 1 < nl
                 y = hip.conv3x3_bias_act_fwd(h, w, b, act, amax_in=am, tap=tap)
                 am = hip.take_amax() if tap else None
             acts.append((h, y))
@@ -987,19 +935,19 @@ class BroadcastDecoderFn(torch.autograd.Function):
             dow = hip.conv2d_direct_wgrad(last, dyo, 1, 1, 0, out=None if gow is None else gow.view(ow4.shape))
             da = hip.conv2d_direct_dgrad(dyo, ow4, last.shape[2], last.shape[3], 1, 0)
             dow, dob = _ret(gow, dow.view(ow.shape)), _ret(gob, dob)
-        elif nl >= 2 and hip.ACTS[act] in (1, 2) and os.environ.get('GENESIS_DGRAD_ACT_FUSE', '1') != '0':
+        elif nl >= 2 and hip.ACTS[act] in (1, 2):
             # the last 3x3 layer's bias + activation backward inside the 1x1 conv's data gradient (`last` is its output)
             gbp = _gout(params[2 * nl - 1])
             wp = params[2 * nl - 2]
-            lazy = QUAD_BIAS and wp.shape[0] == wp.shape[1] and _quad_ok(last.shape[0], wp.shape[1], last.shape[2], last.shape[3])
+            lazy = wp.shape[0] == wp.shape[1] and _quad_ok(last.shape[0], wp.shape[1], last.shape[2], last.shape[3])
             gow, gob = _gout(ow), _gout(ob)
             if gow is None or gob is None:
                 gow = gob = None
             dyl, dow, dob, dbl = hip.conv1x1_bwd_act(last, gfull, ow, ob, act, out=(gow, gob), dbx_out=gbp, want_dbx=not lazy,
-                                                     tap=CHAIN_TAPS)
+                                                     tap=True)
             dow, dob = _ret(gow, dow), _ret(gob, dob)
             pre = (dyl, dbl, gbp)
-            am0 = hip.take_amax() if CHAIN_TAPS else None      # (dyl's partial maxima: the first data gradient's fp16 scale)
+            am0 = hip.take_amax()      # (dyl's partial maxima: the first data gradient's fp16 scale)
         else:
             gow, gob = _gout(ow), _gout(ob)
             if gow is None or gob is None:
@@ -1031,18 +979,14 @@ class BroadcastDecoderFn(torch.autograd.Function):
                     # layer l - 1's bias + activation backward in this data gradient's epilogue (h is its output)
                     gbp = _gout(params[2 * l - 1])
                     wp = params[2 * l - 2]
-                    lazy = QUAD_BIAS and wp.shape[0] == wp.shape[1] and _quad_ok(h.shape[0], wp.shape[1], h.shape[2], h.shape[3])
-                    pre = hip.conv3x3_dgrad_act(dy, w, h, act, gbp, want_dbias=not lazy, amax_in=am, tap=CHAIN_TAPS) + (gbp,)
-                    am = hip.take_amax() if CHAIN_TAPS else None
+                    lazy = wp.shape[0] == wp.shape[1] and _quad_ok(h.shape[0], wp.shape[1], h.shape[2], h.shape[3])
+                    pre = hip.conv3x3_dgrad_act(dy, w, h, act, gbp, want_dbias=not lazy, amax_in=am, tap=True) + (gbp,)
+                    am = hip.take_amax()
                 else:
                     da = hip.conv3x3_dgrad(dy, w, amax_in=am)
                     am = None
             grads[2 * l], grads[2 * l + 1] = _ret(gw, dw), _ret(gb, db)
         return (dz, None, None, None) + tuple(grads)
-
-
-CHAIN_TAPS = os.environ.get('GENESIS_BCAST_CHAIN_TAPS', '1') != '0'   # 0: every canvas conv makes its own amax pass over its input
-QUAD_BIAS = os.environ.get('GENESIS_QUAD_WGRAD_BIAS', '1') != '0'     # 0: the fused data gradients' own plane-sum pass
 
 
 def _quad_ok(N, C, H, W):

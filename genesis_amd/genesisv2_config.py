@@ -335,18 +335,10 @@ class GenesisV2(nn.Module):
         zh = fn.linear(zh, self.z_head[1].weight, self.z_head[1].bias, 'relu')
         zh = fn.linear(zh, self.z_head[3].weight, self.z_head[3].bias)
         z, mu, sigma, log_q = fn.PosteriorFn.apply(zh, eps)                  # [K,B,D] x3, [K,B]
-        # --- Component KL (Genesis.mask_latent_loss, models/genesis_config.py:288-343); optionally forked onto the
-        #     side stream so that its chain of tiny kernels runs beside the decoder (step_state().side_prior)
-        forked = fn.step_state().side_prior and self.prior_lstm is not None and torch.is_grad_enabled()
-        if forked:
-            with fn.side_branch(z, log_q):
-                kl = self._component_kl(z, log_q)
         # --- Decode latents, reconstruction loss
         err, recon, x_r, log_m_r = self._decode(z, x, self.klm_loss and not self.detach_mr_in_klm)
-        if forked:
-            fn.join_branch()
-        else:
-            kl = self._component_kl(z, log_q)
+        # --- Component KL (Genesis.mask_latent_loss, models/genesis_config.py:288-343)
+        kl = self._component_kl(z, log_q)
         t = dict(err=err, kl=kl, recon=recon, log_m=log_m, log_s=log_s, x_r=x_r, log_m_r=log_m_r, colour=colour, seeds=seeds,
                  idx=idx, mu=mu, sigma=sigma, z=z)
         # -- Optional: Attention mask loss (MONet.kl_m_loss, models/monet_config.py:157-170)

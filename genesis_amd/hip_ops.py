@@ -383,17 +383,11 @@ def deconv5x5s2_fwd(x, w, bias):
     return y
 
 
-AMAX_LINK = os.environ.get('GENESIS_AMAX_LINK', '1') != '0'
-AMAX_LINK_REG = os.environ.get('GENESIS_AMAX_LINK_REG', '1') != '0'     # 0: only the decoder head's gradient is handed over
-
-
 def amax_link(device, numel, capacity=16384):
     """gx_kq_amax_link: arms the one-shot hand-over of a tensor's partial maxima from the kernel that writes it (the decoder head's
     GroupNorm backward) to the fp16 x 3 conv that reads it next (gx_deconv5x5s2_dgrad) -- no second pass over a 235 MB gradient.
     numel: the elements of that tensor (a producer launch that covers only part of it leaves the link alone).
     Returns the scratch buffer (keep it alive until the consumer has been enqueued)."""
-    if not AMAX_LINK:
-        return None
     buf = torch.empty(capacity, dtype=F32, device=device)
     # the consumer is enqueued by a LATER call: the scratch must not go back to the allocator (and be handed to the tensors of the
     # calls in between) before that -- the last few links' buffers are kept alive here, whatever the caller does with its reference
@@ -526,7 +520,7 @@ def _conv_gn(kind, x, w, bias, gamma, beta, groups, eps, dst0, dst1, link_out=Fa
     mean = torch.empty(N * groups, dtype=F32, device=x.device)
     rstd = torch.empty(N * groups, dtype=F32, device=x.device)
     need_sum = nsplit.value > 1 or bias is not None
-    link = amax_link(x.device, N * Cout * Ho * Wo) if link_out and AMAX_LINK_REG else None      # noqa: F841  (alive until the launch below is enqueued)
+    link = amax_link(x.device, N * Cout * Ho * Wo) if link_out else None      # noqa: F841  (alive until the launch below is enqueued)
     tap = _tap_begin(x.device, Ho * Wo, N * Cout * Ho * Wo)
     _lib.call('gx_gn_relu_fwd_parts', parts, nsplit.value, stride.value, _p(bias), _p(y) if need_sum else None,
               _p(gamma), _p(beta), N, Cout, Ho, Wo, groups, float(eps),

@@ -253,13 +253,6 @@ def _all_reduce_sum(t, info=None):
     import os
     import torch.distributed as dist
     grp = _SYNC['group']
-    fake = os.environ.get('GENESIS_SYNC_BN_FAKE')
-    if fake:                  # (diagnosis: the partner is a copy of this rank; 2: ... behind a host-blocking barrier)
-        if fake == '2':
-            torch.cuda.synchronize()
-            dist.barrier(group=grp)
-        t.mul_(dist.get_world_size(grp))
-        return
     if t.is_cuda and dist.get_backend(grp) != 'nccl':
         h = t.detach().cpu().contiguous()
         debug = os.environ.get('GENESIS_SYNC_BN_DEBUG') == '1'

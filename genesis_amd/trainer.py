@@ -27,7 +27,7 @@ class TrainStep(object):
 
     def __init__(self, model, img_size, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, geco=None, use_geco=True,
                  beta_fixed=0.5, process_group=None, graph=False, async_wgrad=False, weight_cache=True, defer_reduces=True,
-                 side_prior=None, optimiser='adam', beta_warmup=False, train_iter=None, log_mse=False,
+                 optimiser='adam', beta_warmup=False, train_iter=None, log_mse=False,
                  materialise_stats=False):
         """optimiser: 'adam' (torch.optim.Adam(lr); betas / eps as given), 'rmsprop' (torch.optim.RMSprop(lr): alpha 0.99,
         eps 1e-8) or 'sgd' (torch.optim.SGD(lr, 0.9)) -- train.py:170-176.  use_geco=False: the fixed-beta objective
@@ -54,7 +54,6 @@ class TrainStep(object):
         self.geco = geco if geco is not None else (make_geco(img_size, device=self.device) if use_geco else None)
         self.beta_fixed = beta_fixed
         self.async_wgrad = async_wgrad
-        self.side_prior = (os.environ.get('GENESIS_SIDE_PRIOR', '0') == '1') if side_prior is None else side_prior
         self.defer_reduces = defer_reduces
         self._beta_fixed_t = torch.tensor(float(beta_fixed), device=self.device)
         self.pg = process_group
@@ -70,12 +69,12 @@ class TrainStep(object):
         self.step_t = torch.zeros((), dtype=torch.int64, device=self.device)
         self._mse_ws = self._mse_out = None
         # the step's noise (rand_pixel, eps) from one counter-based launch keyed by (torch's seed + rank, the step counter)
-        # instead of torch.rand + torch.randn and their graph-RNG bookkeeping (GENESIS_HIP_NOISE=0: torch's generators)
+        # instead of torch.rand + torch.randn and their graph-RNG bookkeeping (a model without a noise hook: torch's generators)
         # The hook is on the model only WHILE an iteration of this loop runs (_enter .. _leave): validation / visualisation
         # forwards between two steps draw fresh torch.rand / randn like the reference's (they would otherwise all see the
         # next training step's noise), torch.save(model) keeps working, and two loops on one model cannot clear each
         # other's hook.
-        self._hip_noise = os.environ.get('GENESIS_HIP_NOISE', '1') != '0' and hasattr(model, 'noise')
+        self._hip_noise = hasattr(model, 'noise')
         self._noise_hook = None           # (set only inside an iteration: no reference cycle self -> bound method -> self)
         self.graph = None
         self.graph2 = None
@@ -146,7 +145,6 @@ class TrainStep(object):
         _fn.begin_direct_grads()
         _hip.defer_state().on = self.defer_reduces
         st.async_wgrad = self.async_wgrad
-        st.side_prior = self.side_prior
         st.early_flush = self._early_collective if self._early_range is not None else None
         if self._sync_bn:
             from . import sylvester
@@ -170,7 +168,6 @@ class TrainStep(object):
         st = _fn.step_state()
         st.direct_param_grads = False
         st.async_wgrad = False
-        st.side_prior = False
         st.early_flush = None
         _hip.defer_state().on = False
         _hip.defer_discard()             # no-op after a completed iteration (the queue was flushed)

@@ -50,8 +50,8 @@ int gx_conv3x3_wgrad(const float* x, const float* dy, float* dw, int N, int Cin,
  *      against the direct sum).  mode 0: forward y = conv(x, w); mode 1: data gradient dx from dy (same w [Cout,Cin,3,3]).
  *      Eligible shapes: gx_conv3x3_wino_supported (H % 8 == 0, W % 16 == 0, >= 16 channels). */
 int gx_conv3x3_wino_supported(int N, int Cin, int Cout, int H, int W);
-/*      which layers gx_conv3x3_fwd / _dgrad send to it: 0 none, 1 those whose grid fills the chip (default; also
- *      GENESIS_WINOGRAD=0/1/2 in the environment), 2 every supported shape. */
+/*      which layers gx_conv3x3_fwd / _dgrad send to it: 0 none, 1 those whose grid fills the chip (default),
+ *      2 every supported shape. */
 int gx_conv3x3_wino_policy(int mode);
 /*      which matrix pipe the Winograd layers' products run on (3: one bf16 piece per operand, gx_matmul_precision(2)): 1 (default; GENESIS_WINO_BF16X6=0/1 in the environment) = the
  *      bf16 pipe, every fp32 product U * V from six bf16 piece products accumulated in fp32 (hi + mid + lo pieces hold all 24
@@ -59,10 +59,10 @@ int gx_conv3x3_wino_policy(int mode);
  *      operands are laid out for the pipe in force when they were packed: switch between iterations, not inside one. */
 int gx_wino_precision(int mode);
 /*      k-quad tap-conv kernels (gx_kq.hip: 16-byte k-contiguous MFMA operand reads) behind gx_conv3x3_fwd / _dgrad and
- *      gx_deconv5x5s2_fwd / _dgrad: 0 never, 1 layers whose grid fills the chip (default; GENESIS_KQ=0/1/2 in the
- *      environment), 2 every eligible shape (power-of-two grids, reduction channels a multiple of 8). */
+ *      gx_deconv5x5s2_fwd / _dgrad: 0 never, 1 layers whose grid fills the chip (default),
+ *      2 every eligible shape (power-of-two grids, reduction channels a multiple of 8). */
 int gx_kq_policy(int mode);
-/*      weight gradients of layers of width >= 8 (gx_wgq.hip): 1 (default; GENESIS_WGQ=0/1, GENESIS_WGQ_STREAM=0/1) =
+/*      weight gradients of layers of width >= 8 (gx_wgq.hip): 1 (default) =
  *      LDS-DMA staged kernels, every queued layer in ONE stream-K launch at gx_defer_flush; 2 = the same kernels, one
  *      launch per (tap class, tile width); 0 = the round-1 kernels everywhere. */
 int gx_wgq_policy(int mode);
@@ -78,7 +78,7 @@ int gx_wgq_precision(int mode);
  *      32 / 64, transposed conv from 32 x 32): 1 (default) row-ring tiles -- a tile is one full-width base row, the x rows
  *      roll through a four-slot LDS ring, every operand value is split into its bf16 planes once on its way into LDS and
  *      the taps' column shifts are funnel shifts of the dy operand -- 0 the 64-pixel LDS-DMA tiles whose lanes split
- *      what they read (the A/B reference).  Environment: GENESIS_WGQ_RING=0.  Replaces the same reference ops as
+ *      what they read (the A/B reference).  Replaces the same reference ops as
  *      gx_conv3x3_wgrad / gx_deconv5x5s2_wgrad (modules/blocks.py:159-165, models/genesisv2_config.py:89-99). */
 /*      Mode 2 of gx_wgq_precision (the default since round 6; GENESIS_WGQ_F16X3=0: mode 1): the row-ring tiles form every fp32
  *      product from THREE fp16 piece products (x * 2^e = hi + lo, one power-of-two scale per operand TENSOR) instead of six
@@ -130,7 +130,7 @@ int gx_kq_precision(int mode);
  *      Returns the level in force BEFORE the call, or GX_MATMUL_MIXED when the three families' modes are not one level (set one by
  *      one, or by the per-family environment variables); negative: error.  gx_matmul_precision_get() returns the current level
  *      the same way.  Environment: GENESIS_MATMUL_PRECISION=highest|high|medium, when set, decides all three families' defaults
- *      ahead of GENESIS_KQ_* / GENESIS_WGQ_* / GENESIS_WINO_*; unset, nothing changes.  Packed operands are laid out per mode:
+ *      ahead of the per-family variables (GENESIS_KQ_BF16X6 / GENESIS_KQ_F16X3 and their WGQ / WINO likes); unset, nothing changes.  Packed operands are laid out per mode:
  *      switch between iterations, not inside one.  Several ranks: every rank must set the same level (not checked). */
 #define GX_MATMUL_MIXED 3
 int gx_matmul_precision(int level);
@@ -433,8 +433,7 @@ int gx_bias_act_bwd(const float* out, const float* g, int N, int C, int H, int W
 /*      gx_conv3x3_dgrad_act: the data gradient of a conv3x3 whose input was such a layer's output xout [N,Cin,H,W]
  *      (modules/decoders.py:25-32: Conv2d, ReLU, Conv2d, ...): dxa = dgrad(dy, w) * act'(xout) and dbias [Cin] (NULL to
  *      skip) = sum_{n,hw} dxa -- gx_conv3x3_dgrad followed by gx_bias_act_bwd with the activation's backward in the conv
- *      kernel's epilogue.  Shapes of the bf16-pipe <= 32-channel kernel only: gx_conv3x3_dgrad_act_supported.
- *      Environment: GENESIS_DGRAD_ACT_FUSE=0 (supported() answers 0: the two separate calls). */
+ *      kernel's epilogue.  Shapes of the bf16-pipe <= 32-channel kernel only: gx_conv3x3_dgrad_act_supported. */
 int gx_conv3x3_dgrad_act_supported(int N, int Cin, int Cout, int H, int W);
 size_t gx_conv3x3_dgrad_act_ws_bytes(int N, int Cin, int Cout, int H, int W);
 int gx_conv3x3_dgrad_act(const float* dy, const float* w, const float* xout, int act, float* dxa, float* dbias, int N,

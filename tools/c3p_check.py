@@ -1,6 +1,6 @@
 """The canvas conv (32 -> 32 on [N, 32, 72, 72]) forward (+ bias + ReLU / ELU), data gradient and data gradient with the previous
-layer's activation backward: time per call and a checksum file, so that two runs (GENESIS_KQ_C3P=0 / 1) can be compared bit for bit:
-    GENESIS_KQ_C3P=0 python tools/c3p_check.py /tmp/a.pt; python tools/c3p_check.py /tmp/b.pt /tmp/a.pt"""
+layer's activation backward: time per call and a checksum file, so that two runs (two builds: GENESIS_HIP_LIB) can be compared bit for bit:
+    GENESIS_HIP_LIB=old.so python tools/c3p_check.py /tmp/a.pt; python tools/c3p_check.py /tmp/b.pt /tmp/a.pt"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -2,7 +2,6 @@
 wall time per call (HIP events).  Usage: python tools/check_kq.py"""
 import os, sys, os.path as osp
 sys.path.insert(0, osp.dirname(osp.dirname(osp.abspath(__file__))))
-os.environ['GENESIS_KQ'] = '2'
 import torch
 from genesis_amd import hip_ops as hip, _lib
 
