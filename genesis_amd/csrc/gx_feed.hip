@@ -127,6 +127,12 @@ u8hwc_pil_bilinear_kernel(const unsigned char* __restrict__ src, float* __restri
 // Instance label maps: int [B, Hs, Ws] -> int64 [B, 1, H, W], nearest inside the crop window with F.interpolate's index
 // rule.  The reference moves labels through fp32 (FloatTensor, F.interpolate, .long()); that round trip is the identity on
 // every value an fp32 holds exactly, which this copy is.
+// s = min(floor(d * scale), in - 1) with scale = in / out in fp32: the source index of output index d on one axis.
+__device__ __forceinline__ int nearest_src_index(int d, float scale, int in) {
+    const int s = (int)floorf((float)d * scale);
+    return s < in - 1 ? s : in - 1;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 labels_crop_nearest_kernel(const T* __restrict__ src, long long* __restrict__ dst, int B, int Hs, int Ws, int top, int left,
@@ -137,10 +143,65 @@ labels_crop_nearest_kernel(const T* __restrict__ src, long long* __restrict__ ds
         const int x = (int)(i % W);
         const int y = (int)((i / W) % H);
         const int b = (int)(i / ((size_t)W * H));
-        int sy = (int)floorf((float)y * sh), sx = (int)floorf((float)x * sw);
-        sy = sy < Hc - 1 ? sy : Hc - 1;
-        sx = sx < Wc - 1 ? sx : Wc - 1;
+        const int sy = nearest_src_index(y, sh, Hc), sx = nearest_src_index(x, sw, Wc);
         dst[i] = (long long)src[((size_t)b * Hs + top + sy) * Ws + left + sx];
+    }
+}
+
+// Entity-mask stacks -> instance maps (datasets/multi_object_config.py:188-203): the reference writes o + 1 wherever
+// mask[o] == 255, for o = background_entities .. E - 1 in order, so the highest such o wins; 0 where there is none.  Fused
+// with the crop window and the nearest resample of the kernel above (the same index rule), int64 out.  Byte (b, o, y, x) sits
+// at b * E * Hs * Ws + o * es + (y * Ws + x) * ps: [E, Hs, Ws] stacks (es = Hs * Ws, ps = 1) and [Hs, Ws, E] stacks (es = 1,
+// ps = E: Multi-dSprites, which the reference transposes on the host) are read in place.  Entities are visited from the top
+// down and a pixel stops at its first hit.  Lanes walk x: planar stacks read a plane's row contiguously, interleaved ones
+// read E adjacent bytes a lane, so the wave's lines are fully used over the entity loop.
+__global__ void __launch_bounds__(256)
+entity_masks_to_labels_kernel(const unsigned char* __restrict__ masks, long long* __restrict__ dst, int B, int E, int Hs, int Ws,
+                              long long es, long long ps, int bg, int top, int left, int Hc, int Wc, int H, int W) {
+    const size_t total = (size_t)B * H * W;
+    const float sh = (float)Hc / (float)H, sw = (float)Wc / (float)W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        const int y = (int)((i / W) % H);
+        const int b = (int)(i / ((size_t)W * H));
+        const int sy = nearest_src_index(y, sh, Hc), sx = nearest_src_index(x, sw, Wc);
+        const unsigned char* p = masks + (size_t)b * E * Hs * Ws + ((size_t)(top + sy) * Ws + left + sx) * (size_t)ps;
+        int label = 0;
+        for (int o = E - 1; o >= bg; --o)
+            if (p[(size_t)o * (size_t)es] == 255) {
+                label = o + 1;
+                break;
+            }
+        dst[i] = (long long)label;
+    }
+}
+
+// The same map of a planar stack without a resample (H = Hc, W = Wc), 16 pixels of a row a thread: one aligned 16-byte load
+// per entity plane (a wave reads 1 KB of a plane's rows per instruction) and eight 16-byte stores.  The host takes this path
+// only when every row segment starts on a 16-byte boundary: both bases, Hs * Ws, Ws, left and Wc all multiples of 16.
+__global__ void __launch_bounds__(256)
+entity_masks_to_labels_rows16_kernel(const unsigned char* __restrict__ masks, long long* __restrict__ dst, int B, int E, int Hs,
+                                     int Ws, int bg, int top, int left, int H, int W) {
+    const int wq = W / 16;
+    const size_t total = (size_t)B * H * wq, plane = (size_t)Hs * Ws;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int xq = (int)(i % wq);
+        const int y = (int)((i / wq) % H);
+        const int b = (int)(i / ((size_t)wq * H));
+        const unsigned char* p = masks + (size_t)b * E * plane + (size_t)(top + y) * Ws + left + 16 * xq;
+        unsigned char lab[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) lab[j] = 0;
+        for (int o = bg; o < E; ++o) {                 // ascending, the later entity overwrites: the reference's order
+            const uint4 v = *(const uint4*)(p + (size_t)o * plane);
+            const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (((w[j >> 2] >> (8 * (j & 3))) & 0xffu) == 255u) lab[j] = (unsigned char)(o + 1);
+        }
+        longlong2* q = (longlong2*)(dst + ((size_t)b * H + y) * W + 16 * xq);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = make_longlong2((long long)lab[2 * j], (long long)lab[2 * j + 1]);
     }
 }
 
@@ -298,6 +359,39 @@ int gx_labels_crop_nearest(const void* src, int dtype, long long* dst, int B, in
         hipLaunchKernelGGL(labels_crop_nearest_kernel<long long>, dim3((unsigned)blocks), dim3(256), 0, s,
                            (const long long*)src, dst, B, Hs, Ws, top, left, Hc, Wc, H, W);
     GX_CHECK_LAUNCH("gx_labels_crop_nearest");
+    return GX_OK;
+}
+
+int gx_entity_masks_to_labels(const unsigned char* masks, long long* dst, int B, int E, int Hs, int Ws, long long entity_stride,
+                              long long pixel_stride, int background_entities, int top, int left, int Hc, int Wc, int H, int W,
+                              gx_stream_t stream) {
+    GX_CHECK_ARG(masks && dst, "gx_entity_masks_to_labels: null pointer");
+    GX_CHECK_ARG(B > 0 && E > 0 && E < 255 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && Hc > 0 && Wc > 0,
+                 "gx_entity_masks_to_labels: bad dims");
+    GX_CHECK_ARG(top >= 0 && left >= 0 && top + Hc <= Hs && left + Wc <= Ws,
+                 "gx_entity_masks_to_labels: crop window (%d, %d, %d, %d) outside the %d x %d frame", top, left, Hc, Wc, Hs, Ws);
+    GX_CHECK_ARG(background_entities >= 0, "gx_entity_masks_to_labels: bad background_entities %d", background_entities);
+    const long long plane = (long long)Hs * Ws;
+    GX_CHECK_ARG(entity_stride > 0 && pixel_stride > 0 && entity_stride <= (long long)E * plane && pixel_stride <= (long long)E * plane &&
+                     (E - 1) * entity_stride + (plane - 1) * pixel_stride < (long long)E * plane,
+                 "gx_entity_masks_to_labels: entity stride %lld and pixel stride %lld reach outside a frame's %d x %d x %d bytes",
+                 entity_stride, pixel_stride, E, Hs, Ws);
+    hipStream_t s = (hipStream_t)stream;
+    const bool planar = entity_stride == plane && pixel_stride == 1;
+    const bool rows16 = planar && H == Hc && W == Wc && ((uintptr_t)masks % 16) == 0 && ((uintptr_t)dst % 16) == 0 && plane % 16 == 0 && Ws % 16 == 0 &&
+                        left % 16 == 0 && Wc % 16 == 0;
+    const size_t total = rows16 ? (size_t)B * H * (W / 16) : (size_t)B * H * W;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const int ne = E > background_entities ? E - background_entities : 0;
+    GxProf pf(KID_SMALL_REDUCE, s, 0.0, (double)B * Hc * Wc * ne + 8.0 * B * H * W);
+    if (rows16)
+        hipLaunchKernelGGL(entity_masks_to_labels_rows16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, masks, dst, B, E, Hs, Ws,
+                           background_entities, top, left, H, W);
+    else
+        hipLaunchKernelGGL(entity_masks_to_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, s, masks, dst, B, E, Hs, Ws,
+                           entity_stride, pixel_stride, background_entities, top, left, Hc, Wc, H, W);
+    GX_CHECK_LAUNCH("gx_entity_masks_to_labels");
     return GX_OK;
 }
 

@@ -138,6 +138,44 @@ def transform_labels(labels, size, crop=None, out=None):
     return out
 
 
+_MASK_LAYOUTS = ('ehw', 'hwe')
+
+
+def _mask_dims(shape, layout):
+    """(B, E, Hs, Ws) of a mask stack [B,E,H,W] ('ehw') or [B,H,W,E] ('hwe'), either with a trailing axis of 1 as stored."""
+    if layout not in _MASK_LAYOUTS:
+        raise GenesisHipError('feeder: mask layout must be one of %s, not %r' % (list(_MASK_LAYOUTS), layout))
+    shape = tuple(shape)
+    if len(shape) == 5 and shape[4] == 1:
+        shape = shape[:4]
+    if len(shape) != 4:
+        raise GenesisHipError('feeder: expected a mask stack [B,E,H,W] or [B,H,W,E] (optionally with a last axis of 1), not %s'
+                              % list(shape))
+    return shape if layout == 'ehw' else (shape[0], shape[3], shape[1], shape[2])
+
+
+def entity_masks_to_labels(masks, background_entities, size=None, crop=None, layout='ehw', out=None):
+    """masks: uint8 device stack of per-entity masks, [B,E,Hs,Ws] (layout 'ehw': ObjectsRoom, CLEVR, Tetrominoes) or
+    [B,Hs,Ws,E] ('hwe': Multi-dSprites as stored, which the reference transposes), optionally with the stored last axis of
+    1 -> int64 instance maps [B,1,H,W]: label = o + 1 of the highest entity o >= background_entities whose mask is 255
+    there, 0 if none (datasets/multi_object_config.py:188-203), of the crop window resampled nearest as in
+    transform_labels.  One HIP launch reads the stack in place."""
+    if not masks.is_cuda:
+        raise GenesisHipError('feeder: masks must be on the HIP device; there is no CPU path')
+    if masks.dtype != torch.uint8 or not masks.is_contiguous():
+        raise GenesisHipError('feeder: expected a contiguous uint8 mask stack')
+    B, E, Hs, Ws = _mask_dims(masks.shape, layout)
+    top, left, Hc, Wc, H, W = _size_and_box(Hs, Ws, size, crop)
+    if out is None:
+        out = torch.empty(B, 1, H, W, dtype=torch.int64, device=masks.device)
+    _check_out(out, (B, 1, H, W), torch.int64, masks.device)
+    es, ps = (Hs * Ws, 1) if layout == 'ehw' else (1, E)
+    _lib.call('gx_entity_masks_to_labels', ctypes.c_void_p(masks.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, E, Hs, Ws,
+              es, ps, int(background_entities), top, left, Hc, Wc, H, W,
+              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return out
+
+
 class DeviceFeeder(object):
     """Iterates fp32 device batches from an iterable of uint8 HWC host batches (numpy arrays or CPU tensors
     [B, H, W, C]).  A ring of `depth` slots (pinned staging buffer + uint8 device buffer); the host->device copy of
@@ -156,11 +194,23 @@ class DeviceFeeder(object):
     Other datasets' transforms: `crop` = (top, left, h, w) (centre_box) and `resize` ('nearest' / 'bilinear') as in
     transform_frames.  Dict batches {'input': uint8 [B,H,W,C], 'instances': int [B,H,W] or [B,1,H,W]} (as the reference's
     loaders yield them; 'instances' optional) come out as {'input': fp32 [B,C,S,S], 'instances': int64 [B,1,S,S]}: a slot
-    then holds both buffers, and its `consumed` event is recorded after both conversions."""
+    then holds both buffers, and its `consumed` event is recorded after both conversions.
 
-    def __init__(self, host_batches, img_size, device='cuda', depth=32, crop=None, resize='nearest'):
+    Entity-mask stacks: a dict batch may carry 'masks' instead of 'instances' -- the uint8 stack [B,E,H,W] (mask_layout
+    'ehw') or [B,H,W,E] ('hwe'), optionally with the stored last axis of 1, as the multi-object TFRecord datasets hold it
+    (genesis_amd/multi_object_config.py).  It crosses PCIe as stored and comes out as 'instances' through
+    entity_masks_to_labels with `background_entities`, which must then be given.
+
+    reset(host_batches) starts on a new iterable (the next epoch) and keeps the ring's buffers."""
+
+    def __init__(self, host_batches, img_size, device='cuda', depth=32, crop=None, resize='nearest', background_entities=None,
+                 mask_layout='ehw'):
         if resize not in _RESAMPLE_MODES:
             raise GenesisHipError('feeder: resize must be one of %s, not %r' % (sorted(_RESAMPLE_MODES), resize))
+        if mask_layout not in _MASK_LAYOUTS:
+            raise GenesisHipError('feeder: mask layout must be one of %s, not %r' % (list(_MASK_LAYOUTS), mask_layout))
+        self.background_entities = background_entities
+        self.mask_layout = mask_layout
         self.it = iter(host_batches)
         self.img_size = img_size
         self.crop = crop
@@ -194,10 +244,22 @@ class DeviceFeeder(object):
         is_dict = isinstance(nxt, dict)
         lab = None
         if is_dict:
-            extra = set(nxt) - {'input', 'instances'}
+            extra = set(nxt) - {'input', 'instances', 'masks'}
             if 'input' not in nxt or extra:
-                raise GenesisHipError("feeder: dict batches hold 'input' and optionally 'instances', not %s" % sorted(extra))
+                raise GenesisHipError("feeder: dict batches hold 'input' and optionally 'instances' or 'masks', not %s"
+                                      % sorted(extra))
             t = torch.as_tensor(nxt['input'])
+            if 'masks' in nxt:
+                if 'instances' in nxt:
+                    raise GenesisHipError("feeder: a dict batch holds 'instances' or 'masks', not both")
+                if self.background_entities is None:
+                    raise GenesisHipError("feeder: batches with 'masks' need the background_entities argument")
+                lab = torch.as_tensor(nxt['masks'])
+                if lab.dtype != torch.uint8:
+                    raise GenesisHipError('feeder: entity masks must be uint8, not %s' % lab.dtype)
+                mb, _, mh, mw = _mask_dims(lab.shape, self.mask_layout)
+                if t.dim() != 4 or (mb, mh, mw) != tuple(t.shape[:3]):
+                    raise GenesisHipError('feeder: masks %s do not match the input frames %s' % (list(lab.shape), list(t.shape)))
             if 'instances' in nxt:
                 lab = torch.as_tensor(nxt['instances'])
                 if lab.dim() == 4 and lab.shape[1] == 1:
@@ -245,6 +307,13 @@ class DeviceFeeder(object):
         self.filled[s] = True
         self.tail = (s + 1) % self.depth
 
+    def reset(self, host_batches):
+        """Continues with a new iterable of host batches once the current one is exhausted; the ring's buffers stay."""
+        if any(self.filled):
+            raise GenesisHipError('feeder: reset() before the current batches were all consumed')
+        self.it = iter(host_batches)
+        self._prefetch()
+
     def __iter__(self):
         return self
 
@@ -262,6 +331,9 @@ class DeviceFeeder(object):
             x = {'input': x}
             if 'instances' in self.keys[s]:
                 x['instances'] = transform_labels(self.dev_lab[s], x['input'].shape[2:], self.crop)
+            elif 'masks' in self.keys[s]:
+                x['instances'] = entity_masks_to_labels(self.dev_lab[s], self.background_entities, x['input'].shape[2:],
+                                                        self.crop, self.mask_layout)
         done = torch.cuda.Event()
         done.record(cur)
         self.consumed[s] = done

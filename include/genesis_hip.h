@@ -28,6 +28,7 @@ typedef void* gx_stream_t; /* hipStream_t */
 #define GX_OK 0
 #define GX_EINVAL (-1)  /* bad argument / unsupported shape */
 #define GX_ELAUNCH (-2) /* kernel launch failed */
+#define GX_EDATA (-3)   /* malformed or corrupt input data (TFRecord reader) */
 
 const char* gx_last_error(void);
 int gx_version(void);
@@ -861,6 +862,37 @@ int gx_u8hwc_resample_f32chw(const unsigned char* src, float* dst, int B, int Hs
                              const int* vbounds, const int* vweights, int vksize, gx_stream_t stream);
 int gx_labels_crop_nearest(const void* src, int dtype, long long* dst, int B, int Hs, int Ws, int top, int left, int Hc, int Wc,
                            int H, int W, gx_stream_t stream);
+
+/* ---- the multi-object TFRecord datasets without TensorFlow (datasets/multi_object_config.py, third_party/multi_object_datasets:
+ *      ObjectsRoom, CLEVR with masks, Tetrominoes, Multi-dSprites).  The first four are host only (no GPU, no stream):
+ *      gx_crc32c: CRC-32C (Castagnoli) of n bytes; gx_crc32c_masked: TFRecord's masked form ((c >> 15) | (c << 17)) + 0xa282ead8.
+ *      gx_tfrecord_scan: the complete records in buf[0..n) of a stream framed as u64 length | u32 masked crc of the length |
+ *      data | u32 masked crc of the data: offsets[k] / lengths[k] of the data of up to max_records records, *num_records of
+ *      them, and *consumed = the bytes they occupy from the start of buf.  A trailing partial record is not an error: the
+ *      caller appends more of the stream and scans again.  Both checksums are verified unless verify_crc is 0; a mismatch
+ *      returns GX_EDATA and the message names the record as first_index + k.
+ *      gx_tfexample_find_bytes_list: walks one tf.Example (features(1) -> map entries (key 1, value 2) -> bytes_list(1)) and
+ *      returns the span of the BytesList payload of feature `name` inside rec[0..n); every other field is skipped by wire
+ *      type (float_list, packed or not, int64_list, unknown fields).  GX_EDATA: no such feature, not a bytes_list, or a
+ *      varint / length that runs past the record (never an over-read).
+ *      gx_bytes_list_unpack: the concatenated values of a BytesList payload into dst[0..expected); a list of one-byte values
+ *      (a strict 0A 01 vv stride) takes a fast path.  GX_EDATA unless the values total exactly `expected` bytes.
+ *      gx_entity_masks_to_labels: a uint8 entity-mask stack of B frames -> int64 instance maps [B, 1, H, W]:
+ *      label(p) = max{ o + 1 : o >= background_entities, mask[o, p] == 255 }, 0 if there is none -- what the reference's
+ *      overwrite loop over entities leaves (multi_object_config.py:188-203) -- of the crop window (top, left, Hc, Wc) resampled
+ *      nearest to H x W with gx_labels_crop_nearest's index rule.  mask[b, o, y, x] is the byte at
+ *      b * E * Hs * Ws + o * entity_stride + (y * Ws + x) * pixel_stride, so both stored layouts are read in place:
+ *      [E, Hs, Ws] (entity_stride Hs * Ws, pixel_stride 1) and [Hs, Ws, E] (entity_stride 1, pixel_stride E); every offset
+ *      must stay inside a frame's E * Hs * Ws bytes. */
+unsigned int gx_crc32c(const void* data, size_t n);
+unsigned int gx_crc32c_masked(const void* data, size_t n);
+int gx_tfrecord_scan(const unsigned char* buf, size_t n, int verify_crc, long long first_index, int max_records,
+                     long long* offsets, long long* lengths, int* num_records, size_t* consumed);
+int gx_tfexample_find_bytes_list(const unsigned char* rec, size_t n, const char* name, long long* offset, long long* length);
+int gx_bytes_list_unpack(const unsigned char* payload, size_t n, unsigned char* dst, size_t expected);
+int gx_entity_masks_to_labels(const unsigned char* masks, long long* dst, int B, int E, int Hs, int Ws, long long entity_stride,
+                              long long pixel_stride, int background_entities, int top, int left, int Hc, int Wc, int H, int W,
+                              gx_stream_t stream);
 
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
