@@ -240,4 +240,37 @@ malformed:
     return GX_EDATA;
 }
 
+int gx_bytes_list_index(const unsigned char* payload, size_t n, int max_values, long long* offsets, long long* lengths,
+                        int* count) {
+    GX_CHECK_ARG((payload || n == 0) && offsets && lengths && count, "gx_bytes_list_index: null pointer");
+    GX_CHECK_ARG(max_values >= 0, "gx_bytes_list_index: bad max_values %d", max_values);
+    size_t pos = 0;
+    long long k = 0;
+    *count = 0;
+    while (pos < n) {
+        uint64_t tag;
+        size_t s, l;
+        if (!read_varint(payload, n, &pos, &tag)) goto malformed;
+        if ((tag >> 3) == 1 && (tag & 7) == 2) {
+            if (!read_span(payload, n, &pos, &s, &l)) goto malformed;
+            if (k < max_values) {
+                offsets[k] = (long long)s;
+                lengths[k] = (long long)l;
+            }
+            ++k;                                                // past max_values only counted, for the message
+        } else if (!skip_field(payload, n, &pos, (unsigned)(tag & 7))) {
+            goto malformed;
+        }
+    }
+    if (k > max_values) {
+        gx_set_error("gx_bytes_list_index: the list holds %lld values, the caller gave %d slots", k, max_values);
+        return GX_EDATA;
+    }
+    *count = (int)k;
+    return GX_OK;
+malformed:
+    gx_set_error("gx_bytes_list_index: malformed bytes_list (a varint or a length runs past its %zu bytes)", n);
+    return GX_EDATA;
+}
+
 }  // extern "C"

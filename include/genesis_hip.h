@@ -894,6 +894,35 @@ int gx_entity_masks_to_labels(const unsigned char* masks, long long* dst, int B,
                               long long pixel_stride, int background_entities, int top, int left, int Hc, int Wc, int H, int W,
                               gx_stream_t stream);
 
+/* ---- GQN's JPEG frames without TensorFlow (datasets/gqn_config.py, third_party/tf_gqn/gqn_tfr_provider.py:141-143:
+ *      tf.image.decode_jpeg + convert_image_dtype).  Baseline JPEG split in two: the serial part (markers, Huffman codes) on
+ *      the host, everything that touches a pixel in one kernel.  The first three are host only (no GPU, no stream).
+ *      gx_bytes_list_index: offsets[k] / lengths[k] of every value of a BytesList payload (GQN's `frames`: ten JPEG strings of
+ *      different lengths), *count of them; GX_EDATA when the list holds more than max_values or a length runs past the payload.
+ *      gx_jpeg_info: the geometry of one stream, info[8] = width, height, components (3), sampling class (0 = 4:4:4,
+ *      1 = 4:2:2 / chroma h2v1, 2 = 4:2:0 / chroma h2v2), blocks of the Y, Cb and Cr planes, restart interval.  A plane is
+ *      padded to whole MCUs.
+ *      gx_jpeg_entropy_decode: the same info, plus coef = per component the blocks of its padded plane in raster order (Y, then
+ *      Cb, then Cr), each 64 QUANTISED int16 coefficients in natural (row-major) order with the DC prediction undone
+ *      (coef_capacity counts int16 values), and qtab = three 64-entry tables, one per component, natural order.
+ *      Accepted: SOF0, 8-bit samples, three components in one interleaved scan, luma 1x1 / 2x1 / 2x2 with chroma 1x1, 8-bit
+ *      quantisation tables, any Huffman tables, DRI / RSTn, byte stuffing; APPn and COM are skipped.  GX_EDATA, with a message
+ *      that names the case, for: progressive / extended SOF, arithmetic coding, one or four components, other sampling
+ *      factors, 16-bit tables, frames above 128 x 128, a code that is not in its table, a coefficient index past 63, a
+ *      stream that ends early.  No input makes them read or write out of bounds.
+ *      gx_jpeg_decode_f32chw: B frames of one size H x W (<= 128 x 128) and one sampling class, coef [B][blocks][64] and qtab
+ *      [B][3][64] on the device (16-byte aligned) -> dst_f32 [B, 3, S_h, S_w] = u8 * (1.0f / 255.0f) (TensorFlow's
+ *      convert_image_dtype), resampled with F.interpolate's nearest index when (S_h, S_w) != (H, W), and / or dst_u8
+ *      [B, H, W, 3] at the stored size; either may be NULL.  One launch, one workgroup per frame: dequantisation, the 13-bit
+ *      fixed-point inverse DCT (columns, then rows), triangle-filter chroma upsampling and the 16-bit fixed-point YCbCr -> RGB
+ *      conversion of libjpeg's default decoding path, bit for bit. */
+int gx_bytes_list_index(const unsigned char* payload, size_t n, int max_values, long long* offsets, long long* lengths, int* count);
+int gx_jpeg_info(const unsigned char* data, size_t len, int* info);
+int gx_jpeg_entropy_decode(const unsigned char* data, size_t len, short* coef, size_t coef_capacity, unsigned short* qtab,
+                           int* info);
+int gx_jpeg_decode_f32chw(const short* coef, const unsigned short* qtab, float* dst_f32, unsigned char* dst_u8, int B, int H, int W,
+                          int sampling, int S_h, int S_w, gx_stream_t stream);
+
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
  *      bucket (parameters' gradients + the err / kl tail, genesis_amd/dp.py) is summed IN PLACE over the ranks by one
