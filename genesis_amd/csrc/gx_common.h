@@ -69,6 +69,10 @@ bool gx_defer_push_gn(const GxGnRed& r);
 int gx_defer_flush_wgrad(const GxWgradRed* items, int n, hipStream_t s);   // gx_conv.hip
 int gx_defer_flush_gn(const GxGnRed* items, int n, hipStream_t s);         // gx_norm.hip
 
+// ---- PNG frames (gx_png.cpp, gx_png.hip): the largest width and height.  gx_png_unfilter hands the last row of a band to the
+// next band through kGxPngMaxDim * C bytes of LDS (16 KB for RGBA); the host checks reject larger frames with this same constant.
+constexpr int kGxPngMaxDim = 4096;
+
 static inline int gx_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int gx_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int gx_round_up(int a, int b) { return gx_ceil_div(a, b) * b; }

@@ -923,6 +923,37 @@ int gx_jpeg_entropy_decode(const unsigned char* data, size_t len, short* coef, s
 int gx_jpeg_decode_f32chw(const short* coef, const unsigned short* qtab, float* dst_f32, unsigned char* dst_u8, int B, int H, int W,
                           int sampling, int S_h, int S_w, gx_stream_t stream);
 
+/* ---- PNG frames without Pillow (datasets/shapestacks_config.py:141, datasets/sketchy_config.py:91: Image.open; ShapeStacks'
+ *      .map files are PNGs too).  Split like the JPEG path: the serial part (chunk walk, CRC-32, zlib inflate) on the host,
+ *      everything that touches a pixel on the device.  The first two are host only (no GPU, no stream); inflate and CRC-32 are
+ *      zlib's, resolved from libz.so.1 at first use (GX_EINVAL with a message that says so when it is missing).
+ *      gx_png_info: the geometry of one stream from its signature and IHDR, info[8] = width, height, channels C, bytes per
+ *      pixel (= C), colour type, bit depth, interlace flag, inflated size H * (1 + W * C).
+ *      gx_png_inflate: the same info, and dst[0 .. H * (1 + W * C)) = the inflated IDAT data, STILL FILTERED: per row one filter
+ *      byte and W * C bytes.  Checks the signature, walks the chunks, verifies every chunk's CRC-32, concatenates the IDAT
+ *      payloads, requires the inflated size to be exact and every filter byte to be at most 4.  dst_capacity counts bytes.
+ *      Accepted: 8-bit samples, not interlaced, colour type 0 (grey, C = 1), 2 (RGB, C = 3) or 6 (RGBA, C = 4); ancillary
+ *      chunks and a suggested palette are skipped.  GX_EDATA, with a message that names the case, for: 16-bit samples, samples
+ *      under 8 bits, palette, grey+alpha, Adam7 interlacing, a CRC mismatch (the message names the chunk), a missing IHDR,
+ *      IDAT or IEND, IDAT chunks that are not consecutive, a stream that ends early, an unknown critical chunk, an inflated size other than the expected one, a
+ *      filter byte above 4, frames above 4096 x 4096 (the kernel's bound).  No input makes them read or write out of bounds.
+ *      gx_png_unfilter: B frames of one geometry, filtered [B][H * (1 + W * C)] on the device as gx_png_inflate leaves them ->
+ *      dst_u8 [B, H, W, C], the bytes reconstructed from the five filters (None, Sub, Up, Average = floor((a + b) / 2) on
+ *      9-bit sums, Paeth with ties in the order a, b, c; per byte, the left neighbour C bytes back, 0 outside the frame),
+ *      and / or dst_plane0 [B, H, W] = channel 0 of every pixel after plane_rule: GX_PNG_PLANE_BYTE the byte itself,
+ *      GX_PNG_PLANE_SHAPESTACKS_REF what the reference makes of a ShapeStacks map ((byte / 255.0f) / 32 truncated
+ *      (third_party/shapestacks/segmentation_utils.py:38-41 and .long()): 0 for every byte), GX_PNG_PLANE_INDEX byte >> 5.
+ *      Either may be NULL.  One launch, one workgroup per frame: a skewed wavefront over bands of 1024 / C rows, thread =
+ *      (row, channel byte), neighbouring rows handing values over by cross-lane moves and, between waves, through LDS; the
+ *      frame stays in global memory.  H and W at most 4096, C = 1, 3 or 4. */
+#define GX_PNG_PLANE_BYTE 0
+#define GX_PNG_PLANE_SHAPESTACKS_REF 1
+#define GX_PNG_PLANE_INDEX 2
+int gx_png_info(const unsigned char* data, size_t len, int* info);
+int gx_png_inflate(const unsigned char* data, size_t len, unsigned char* dst, size_t dst_capacity, int* info);
+int gx_png_unfilter(const unsigned char* filtered, unsigned char* dst_u8, unsigned char* dst_plane0, int plane_rule, int B, int H,
+                    int W, int C, gx_stream_t stream);
+
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
  *      bucket (parameters' gradients + the err / kl tail, genesis_amd/dp.py) is summed IN PLACE over the ranks by one
