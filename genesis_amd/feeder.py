@@ -176,6 +176,99 @@ def entity_masks_to_labels(masks, background_entities, size=None, crop=None, lay
     return out
 
 
+_ROW_DTYPES = {torch.uint8: 0, torch.float32: 1}
+_ROW_LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3, torch.float64: 4}
+SPRITE_SIZE = 64
+MAX_SPRITES_PER_IMAGE = 4
+
+
+def _gather_args(src, idx, first, B, what):
+    if not src.is_cuda:
+        raise GenesisHipError('feeder: %s must be on the HIP device; there is no CPU path' % what)
+    if idx is not None and (not idx.is_cuda or idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous()):
+        raise GenesisHipError('feeder: idx must be a contiguous int64 vector on the HIP device')
+    n = src.shape[0] if idx is None else idx.shape[0]
+    first = int(first)
+    B = n - first if B is None else int(B)
+    if first < 0 or B <= 0 or first + B > n:
+        raise GenesisHipError('feeder: rows %d .. %d reach outside the %d %s' % (first, first + B, n,
+                                                                                'rows stored' if idx is None else 'indices'))
+    return first, B, (None if idx is None else ctypes.c_void_p(idx.data_ptr())), (0 if idx is None else int(idx.shape[0]))
+
+
+def _square(size, Hs, Ws):
+    if size is None:
+        return Hs, Ws
+    return (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+
+
+def rows_gather(src, idx=None, first=0, B=None, size=None, out=None):
+    """src: uint8 or float32 device tensor [N, Hs, Ws, C], a whole split as stored -> float32 [B, C, H, W]: the rows
+    idx[first : first + B] of it (idx: int64 device vector, e.g. an epoch's permutation; None: the rows first : first + B
+    themselves), uint8 / 255 and float32 unchanged (ToTensor's two cases), resampled nearest like F.interpolate(size=) when
+    size differs from the stored one.  One HIP launch on the current stream and nothing else: no copy, no synchronisation.
+    The values of idx are NOT checked (that would read them back): the caller checks them on the host before uploading."""
+    if src.dtype not in _ROW_DTYPES or src.dim() != 4 or not src.is_contiguous():
+        raise GenesisHipError('feeder: expected a contiguous uint8 or float32 [N,H,W,C] tensor, not %s %s'
+                              % (src.dtype, list(src.shape)))
+    first, B, pidx, nidx = _gather_args(src, idx, first, B, 'frames')
+    N, Hs, Ws, C = src.shape
+    H, W = _square(size, Hs, Ws)
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=src.device)
+    _check_out(out, (B, C, H, W), torch.float32, src.device)
+    _lib.call('gx_rows_gather_f32chw', ctypes.c_void_p(src.data_ptr()), _ROW_DTYPES[src.dtype], N, pidx, nidx, first,
+              ctypes.c_void_p(out.data_ptr()), B, Hs, Ws, C, H, W, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def rows_gather_labels(src, idx=None, first=0, B=None, size=None, out=None):
+    """src: uint8 / int32 / int64 / float32 / float64 device tensor [N, Hs, Ws] or [N, Hs, Ws, 1] of label maps -> int64
+    [B, 1, H, W]: the same rows as rows_gather, nearest, converted by truncation (datasets/multid_config.py:137-143:
+    ToTensor, F.interpolate, .type(LongTensor))."""
+    if src.dim() == 4 and src.shape[3] == 1:
+        src = src[..., 0]
+    if src.dtype not in _ROW_LABEL_DTYPES or src.dim() != 3 or not src.is_contiguous():
+        raise GenesisHipError('feeder: expected contiguous uint8 / int32 / int64 / float32 / float64 label maps [N,H,W] or '
+                              '[N,H,W,1], not %s %s' % (src.dtype, list(src.shape)))
+    first, B, pidx, nidx = _gather_args(src, idx, first, B, 'label maps')
+    N, Hs, Ws = src.shape
+    H, W = _square(size, Hs, Ws)
+    if out is None:
+        out = torch.empty(B, 1, H, W, dtype=torch.int64, device=src.device)
+    _check_out(out, (B, 1, H, W), torch.int64, src.device)
+    _lib.call('gx_rows_gather_labels', ctypes.c_void_p(src.data_ptr()), _ROW_LABEL_DTYPES[src.dtype], N, pidx, nidx, first,
+              ctypes.c_void_p(out.data_ptr()), B, Hs, Ws, H, W, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def sprites_compose(sprites, first, count, colours, img=None, mask=None):
+    """The pasting loop of scripts/generate_multid.py:47-73 for n images in one HIP launch.  sprites: uint8 device stack
+    [S, 64, 64] (non-zero = set); first, count: int32 device vectors [n], image i pastes sprites first[i] ..
+    first[i] + count[i] - 1 in that order (count 0..4); colours: uint8 device [n, 5, 3], the background and then the
+    objects.  -> (img float32 [n, 64, 64, 3] = byte / 255, mask uint8 [n, 64, 64]); the last sprite covering a pixel wins.
+    The caller checks first + count against S on the host."""
+    n = int(first.shape[0])
+    for t, dtype, shape, name in ((sprites, torch.uint8, (sprites.shape[0], SPRITE_SIZE, SPRITE_SIZE), 'sprites'),
+                                  (first, torch.int32, (n,), 'first'), (count, torch.int32, (n,), 'count'),
+                                  (colours, torch.uint8, (n, MAX_SPRITES_PER_IMAGE + 1, 3), 'colours')):
+        if not t.is_cuda:
+            raise GenesisHipError('feeder: %s must be on the HIP device; there is no CPU path' % name)
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise GenesisHipError('feeder: %s must be a contiguous %s tensor of shape %s, not %s %s'
+                                  % (name, dtype, list(shape), t.dtype, list(t.shape)))
+    if img is None:
+        img = torch.empty(n, SPRITE_SIZE, SPRITE_SIZE, 3, dtype=torch.float32, device=sprites.device)
+    if mask is None:
+        mask = torch.empty(n, SPRITE_SIZE, SPRITE_SIZE, dtype=torch.uint8, device=sprites.device)
+    _check_out(img, (n, SPRITE_SIZE, SPRITE_SIZE, 3), torch.float32, sprites.device)
+    _check_out(mask, (n, SPRITE_SIZE, SPRITE_SIZE), torch.uint8, sprites.device)
+    _lib.call('gx_sprites_compose', ctypes.c_void_p(sprites.data_ptr()), int(sprites.shape[0]), ctypes.c_void_p(first.data_ptr()),
+              ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(colours.data_ptr()), ctypes.c_void_p(img.data_ptr()),
+              ctypes.c_void_p(mask.data_ptr()), n, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return img, mask
+
+
 class DeviceFeeder(object):
     """Iterates fp32 device batches from an iterable of uint8 HWC host batches (numpy arrays or CPU tensors
     [B, H, W, C]).  A ring of `depth` slots (pinned staging buffer + uint8 device buffer); the host->device copy of

@@ -863,6 +863,34 @@ int gx_u8hwc_resample_f32chw(const unsigned char* src, float* dst, int B, int Hs
 int gx_labels_crop_nearest(const void* src, int dtype, long long* dst, int B, int Hs, int Ws, int top, int left, int Hc, int Wc,
                            int H, int W, gx_stream_t stream);
 
+/* ---- Multi-dSprites on the device (datasets/multid_config.py:113-143 dSpritesDataset; scripts/generate_multid.py:37-76).
+ *      The stored split ([N, 64, 64, 3] float32 already / 255, or uint8; label maps [N, 64, 64] in any of five dtypes) is
+ *      resident in device memory; a batch is a gather of B of its rows, the rows idx[first .. first + B) of a DEVICE index
+ *      vector of idx_len int64 entries (an epoch's permutation), or, with idx NULL, the rows first .. first + B themselves
+ *      (a staged batch).  N is the row count of src.  first + B must not pass idx_len (without idx: N); the VALUES of idx
+ *      are not looked at by the library: the caller checks them against [0, N) before it uploads them.
+ *      gx_rows_gather_f32chw: src [N, Hs, Ws, C] (dtype GX_ROWS_U8: value / 255, a true fp32 division as in
+ *      gx_u8hwc_to_f32chw; GX_ROWS_F32: copied unchanged) -> dst fp32 [B, C, H, W], resampled nearest with
+ *      gx_u8hwc_to_f32chw's index rule when (H, W) != (Hs, Ws): ToTensor + F.interpolate(size) (multid_config.py:131-135).
+ *      gx_rows_gather_labels: src [N, Hs, Ws] (GX_LABEL_U8 / _I32 / _I64 / _F32 / _F64) -> dst int64 [B, 1, H, W], the same
+ *      nearest rule and a truncating conversion: what ToTensor + F.interpolate + .type(LongTensor) leave
+ *      (multid_config.py:137-143) for every label a float holds exactly.
+ *      gx_sprites_compose: the loop body of generate_multid.py:47-73 for n images.  sprites uint8 [S, 64, 64] (non-zero =
+ *      set, as np.array(..., dtype=bool)); image i pastes the count[i] (0..4) consecutive sprites from first[i], in that
+ *      order; colours uint8 [n, 5, 3] = background, then the objects.  img fp32 [n, 64, 64, 3] = byte / 255 and mask uint8
+ *      [n, 64, 64]: a pixel takes the colour and the label o + 1 of the LAST sprite o that covers it, else the background
+ *      colour and 0.  first / count / colours are device arrays; the caller checks first[i] + count[i] <= S. */
+#define GX_ROWS_U8 0
+#define GX_ROWS_F32 1
+#define GX_LABEL_F32 3
+#define GX_LABEL_F64 4
+int gx_rows_gather_f32chw(const void* src, int dtype, long long N, const long long* idx, long long idx_len, long long first,
+                          float* dst, int B, int Hs, int Ws, int C, int H, int W, gx_stream_t stream);
+int gx_rows_gather_labels(const void* src, int dtype, long long N, const long long* idx, long long idx_len, long long first,
+                          long long* dst, int B, int Hs, int Ws, int H, int W, gx_stream_t stream);
+int gx_sprites_compose(const unsigned char* sprites, int S, const int* first, const int* count, const unsigned char* colours,
+                       float* img, unsigned char* mask, int n, gx_stream_t stream);
+
 /* ---- the multi-object TFRecord datasets without TensorFlow (datasets/multi_object_config.py, third_party/multi_object_datasets:
  *      ObjectsRoom, CLEVR with masks, Tetrominoes, Multi-dSprites).  The first four are host only (no GPU, no stream):
  *      gx_crc32c: CRC-32C (Castagnoli) of n bytes; gx_crc32c_masked: TFRecord's masked form ((c >> 15) | (c << 17)) + 0xa282ead8.
