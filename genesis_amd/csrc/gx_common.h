@@ -95,6 +95,16 @@ __device__ __forceinline__ int gx_xcd_tile(int bid, int nwg) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// May planes of HW floats of these tensors be walked with 16-byte (f32x4) accesses?  HW % 4 == 0 puts every plane a multiple of
+// 16 bytes behind its tensor's base, so the bases decide -- and a base need not be an allocation: a contiguous slice at an odd
+// element offset of a larger buffer is a legal operand of every entry point.  One predicate for the statistics, apply and pooling
+// kernels (null pointers count as aligned).
+__host__ __device__ __forceinline__ bool gx_vec4_ok(int HW, const void* a, const void* b = nullptr, const void* c = nullptr,
+                                                    const void* d = nullptr) {
+    return (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+                              reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
 // 64-lane wavefront reductions (CDNA4: wave = 64).
 __device__ __forceinline__ float gx_wave_sum(float v) {
 #pragma unroll

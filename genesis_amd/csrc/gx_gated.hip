@@ -52,9 +52,10 @@ gated_stats_partial_kernel(const float* __restrict__ y, const float* __restrict_
     if (nb > n0 + nc) nb = n0 + nc;
     const float b = bias ? bias[ch] : 0.f;
     double acc[2] = {0.0, 0.0};
+    const bool vec = gx_vec4_ok(HW, y);
     for (int n = na; n < nb; ++n) {
         const float* p = y + ((size_t)n * C2 + ch) * HW;
-        if ((HW & 3) == 0) {
+        if (vec) {
             const f32x4* p4 = reinterpret_cast<const f32x4*>(p);
             for (int i = threadIdx.x; i < (HW >> 2); i += blockDim.x) {
                 const f32x4 t = p4[i];
@@ -206,7 +207,7 @@ gated_apply_kernel(const float* __restrict__ y, const float* __restrict__ bias, 
     float* po = out + (size_t)plane * HW;
     float am = 0.f;
     // 16-byte accesses where the planes allow them (every layer of the sylvester stacks): the scalar loop moved 2.5 TB/s
-    if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
+    if (gx_vec4_ok(HW, y, out)) {
         const f32x4* ph4 = reinterpret_cast<const f32x4*>(ph);
         const f32x4* pg4 = reinterpret_cast<const f32x4*>(pg);
         f32x4* po4 = reinterpret_cast<f32x4*>(po);
@@ -254,6 +255,7 @@ gated_bwd_sums_kernel(const float* __restrict__ y, const float* __restrict__ bia
     const float b_h = bias ? bias[c] : 0.f, b_g = bias ? bias[C + c] : 0.f;
     const float g_h = gh ? gh[c] : 1.f, be_h = bh ? bh[c] : 0.f, g_g = gg ? gg[c] : 1.f, be_g = bg ? bg[c] : 0.f;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};             // h: S1, S2; g: S1, S2
+    const bool vec = gx_vec4_ok(HW, y, dout);
     for (int n = na; n < nb; ++n) {
         float mh, rh, mg, rg;
         unit_stats(stats, norm, n, c, C2, &mh, &rh);
@@ -269,7 +271,7 @@ gated_bwd_sums_kernel(const float* __restrict__ y, const float* __restrict__ bia
             acc[0] += (double)dAh; acc[1] += (double)dAh * xh;
             acc[2] += (double)dAg; acc[3] += (double)dAg * xg;
         };
-        if ((HW & 3) == 0) {
+        if (vec) {
             const f32x4* ph4 = reinterpret_cast<const f32x4*>(ph);
             const f32x4* pg4 = reinterpret_cast<const f32x4*>(pg);
             const f32x4* pd4 = reinterpret_cast<const f32x4*>(pd);
@@ -355,7 +357,7 @@ gated_bwd_apply_kernel(const float* __restrict__ y, const float* __restrict__ bi
     float* dh = dy + ((size_t)n * C2 + c) * HW;
     float* dg = dy + ((size_t)n * C2 + C + c) * HW;
     float am = 0.f;
-    if ((HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0) {
+    if (gx_vec4_ok(HW, y, dout, dy)) {
         // (16-byte accesses, as in gated_apply_kernel)
         const f32x4* ph4 = reinterpret_cast<const f32x4*>(ph);
         const f32x4* pg4 = reinterpret_cast<const f32x4*>(pg);

@@ -61,7 +61,7 @@ plane_sum_kernel(const float* __restrict__ x, int HW, float* __restrict__ part) 
     __shared__ double red[4];
     const float* p = x + (size_t)blockIdx.x * HW;
     double s = 0.0;
-    if ((HW & 3) == 0) {
+    if (gx_vec4_ok(HW, x)) {
         for (int i = threadIdx.x; i < HW / 4; i += blockDim.x) {
             const float4 v = reinterpret_cast<const float4*>(p)[i];
             s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);

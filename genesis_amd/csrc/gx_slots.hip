@@ -60,7 +60,7 @@ maskpool_fwd_kernel(const float* __restrict__ f, const float* __restrict__ log_m
         for (int c = 0; c < PCH; ++c) acc[k][c] = 0.0;
     }
     const float* fb = f + ((size_t)b * C + c0) * HW;
-    if ((HW & 3) == 0) {
+    if (gx_vec4_ok(HW, f, log_m)) {
         // 16-byte loads, 4 pixels per thread and iteration: 4x fewer serial load -> use steps (the loop is latency-bound);
         // the loads of iteration i + 1 are issued ahead of iteration i's sums (two register sets): at 64 x 64 a thread has four
         // iterations, each of which used to start with its 4 + K loads' full latency
@@ -767,7 +767,7 @@ int gx_maskpool_bwd(const float* f, const float* log_m, const float* gS, const f
     const int HW = H * W;
     {
         GxProf pf(KID_MASKPOOL_BWD, (hipStream_t)stream, 4.0 * B * K * C * HW, 4.0 * B * HW * (2.0 * C + 2.0 * K));
-        if ((HW & 3) == 0) {
+        if (gx_vec4_ok(HW, f, log_m, df, dlog_m)) {
 #define GX_MP_BWD(KT_)                                                                                                 \
             hipLaunchKernelGGL(maskpool_bwd_vec_kernel<KT_>, dim3(B, gx_ceil_div(HW, 256)), dim3(256),                \
                                (size_t)(((K * C + 3) & ~3) + 4 * K * 64 * 4) * sizeof(float), (hipStream_t)stream, f,   \
