@@ -796,6 +796,25 @@ int gx_gn_relu_fwd_parts(const float* parts, int nsplit, size_t split_stride, co
  *      [B, HW] as the reference's instance maps / argmax outputs are.  Bit-exact integer work. */
 int gx_label_contingency(const long long* segA, const long long* segB, int B, int HW, int KA, int KB, int* counts,
                          gx_stream_t stream);
+/*      gx_seg_metrics: one batch of the validation loop (train.py:534-559) in one launch, from the K log-mask planes read in
+ *      place and the instance map to every score: prediction = argmax_k of the log-masks (ties: lowest k; a NaN ranks above every
+ *      number and the first one wins, as torch.argmax), the table [max_labels, K] of (ground truth, prediction) in LDS, then per
+ *      image b the row rows[b] = (ARI, foreground ARI, mean covering, mean covering without background, scaled covering, scaled
+ *      covering without background, counted pixels, ground-truth labels present) in fp64 -- ARI from int64 pair counts with the
+ *      final expression in fp64 (1.0 when the partitions agree or no pixel is counted), covering in float32 with the labels
+ *      added in ascending order.  Ground-truth labels < 0 are ignore regions (skipped); labels >= max_labels are not counted
+ *      and add one each to state[2].  The last workgroup to finish adds the batch means (fp64 for ARI, float32 for covering,
+ *      image order) to acc[0..8) -- the covering sums themselves kept in float32, as the reference adds its batch means --,
+ *      increments state[1], copies the rows to log[state[3] ..] while they fit into log_capacity rows (log may be NULL) and
+ *      advances state[3].  Planes: either base != NULL, plane k of image b at base + k plane_stride + b image_stride floats
+ *      (planes == NULL), or planes = a HOST array of K device pointers to image 0 of each plane (base == NULL, plane_stride
+ *      ignored), image b image_stride floats further; every plane is HW contiguous floats.  16-byte loads when HW % 4 == 0
+ *      and every plane of every image is 16-byte aligned, 4-byte loads otherwise.  1 <= K <= 32, max_labels * K * 4 bytes
+ *      <= 64 KiB.  instances int64 [B, HW]; rows fp64 [B, 8] (scratch); acc fp64 [8] and state [4] = (arrival counter,
+ *      batches, overflowed pixels, log cursor) zero before the first launch; launches on one stream may share them. */
+int gx_seg_metrics(const float* base, long long plane_stride, long long image_stride, const float* const* planes,
+                   const long long* instances, int B, int HW, int K, int max_labels, double* rows, double* acc,
+                   unsigned long long* state, double* log, long long log_capacity, gx_stream_t stream);
 
 /* ---- FID on the device (scripts/compute_fid.py + third_party/pytorch_fid; genesis_amd/fid.py): pytorch_fid's FID Inception
  *      (Inception-v3, BatchNorm folded into the conv weights by the caller) on NHWC fp32 activations, and the moments of its
