@@ -7,7 +7,8 @@
  * point replaces the ATen op group the reference executes at the cited file:line.
  *
  * Conventions:
- *   - arguments are raw device pointers + explicit sizes; tensors are contiguous NCHW fp32;
+ *   - arguments are raw device pointers + explicit sizes; tensors are contiguous NCHW fp32 (gx_vis_compose, which writes
+ *     the TensorBoard image grids, takes its many sources through a device table of descriptors instead: see there);
  *   - the caller (PyTorch caching allocator) owns every buffer, including workspaces, whose
  *     required size is returned by the matching *_ws_bytes() query;
  *   - every call only ENQUEUES work on `stream` (a hipStream_t); no allocation, no sync;
@@ -815,6 +816,75 @@ int gx_label_contingency(const long long* segA, const long long* segB, int B, in
 int gx_seg_metrics(const float* base, long long plane_stride, long long image_stride, const float* const* planes,
                    const long long* instances, int B, int HW, int K, int max_labels, double* rows, double* acc,
                    unsigned long long* state, double* log, long long log_capacity, gx_stream_t stream);
+
+/* ---- TensorBoard image grids on the device (train.py:423-476 visualise_outputs, utils/misc.py:82-98 colour_seg_masks,
+ *      torchvision.utils.make_grid; genesis_amd/visualise.py).  gx_vis_compose: ONE launch fills a whole atlas -- `atlas`, a flat
+ *      device buffer of atlas_words 4-byte words holding any number of grids back to back, its LAST word an unsigned overflow
+ *      counter (zero before the launch) -- from n_grids descriptors of GX_VIS_DESC_WORDS int64 words each.  The descriptors
+ *      (and, behind them, the pointer tables of ARGMAX_COLOUR grids) form one table of table_words words that the caller holds
+ *      twice with the same contents: table_host is validated here before anything is launched, table_dev is what the kernel
+ *      reads.  Descriptor words (GX_VIS_D_*):
+ *        SRC0, SRC1      device addresses; STRIDE0, STRIDE1 element strides (see the kinds); every source image is contiguous
+ *        DST             first atlas word of the grid;  WORK  first work item of the grid = sum over the grids before it of
+ *                        ITEMS + (OWN_PAD ? Hg Wg : 0);  ITEMS  n H W / 4 when VEC else n H W
+ *        KIND, N, C, H, W, K, NROW, PADDING, PAD_VALUE (the bits of a float in the low half), MODE, VEC, PACKED
+ *        CELL0, N_GEOM, OWN_PAD   the N images fill the cells CELL0 .. CELL0 + N - 1 of a grid laid out for N_GEOM images;
+ *                        a make_grid call is one descriptor with CELL0 = 0, N_GEOM = N, OWN_PAD = 1.  Several descriptors with
+ *                        one DST, geometry and MODE compose a sheet whose cells come from different sources: exactly one of
+ *                        them has OWN_PAD = 1, and every cell below N_GEOM belongs to exactly one of them.
+ *      Geometry (make_grid(nrow, padding, pad_value), normalize=False): xmaps = min(NROW, N_GEOM), ymaps = ceil(N_GEOM / xmaps),
+ *      p = PADDING (0 when N_GEOM == 1: the bare image, as torchvision returns it), Hg = ymaps (H + p) + p, Wg = xmaps (W + p) + p;
+ *      cell i has its first pixel at row (i / xmaps)(H + p) + p, column (i % xmaps)(W + p) + p; every pixel outside the cells
+ *      0 .. N_GEOM - 1 is written with PAD_VALUE by the OWN_PAD descriptor (the kernel writes the padding itself).
+ *      Kinds: GX_VIS_COPY fp32 [N, C, H, W] at SRC0, image stride STRIDE0, C = 1 (written to all three channels) or 3;
+ *      GX_VIS_EXP expf (the accurate one: exp(-1e10) = exp(-inf) = 0 and exp(0) = 1 exactly) of an fp32 [N, 1, H, W] plane;
+ *      GX_VIS_EXP_MUL x expf(m), x [N, 3, H, W] at SRC0 / STRIDE0, m [N, 1, H, W] at SRC1 / STRIDE1, one fp32 rounding each;
+ *      GX_VIS_LABEL_COLOUR int64 [N, 1, H, W] labels -> palette[label], black for a negative label, black and one more in the
+ *      overflow counter for a label >= P; GX_VIS_ARGMAX_COLOUR K fp32 planes [N, 1, H, W] read in place -> argmax (ties: lowest
+ *      k; a NaN ranks above every number and the first one wins, as gx_seg_metrics and torch.argmax) -> palette colour, overflow
+ *      as for labels; PACKED = 1: plane k at SRC0 + k STRIDE1 floats, else SRC1 = the WORD index in the table of K device
+ *      addresses; image b STRIDE0 floats further either way; GX_VIS_FILL no source: the cells hold PAD_VALUE.
+ *      palette: P <= 256 RGB byte triples on the device (may be NULL when no colour kind is present).
+ *      Modes: GX_VIS_FP32_CHW fp32 [3, Hg, Wg] (3 Hg Wg words; colour bytes 0..255 are exact); GX_VIS_U8_HWC bytes [Hg, Wg, 3]
+ *      (ceil(3 Hg Wg / 4) words): rint(clamp(v, 0, 1) 255), half to even; colour kinds write the palette byte itself.
+ *      One thread per source vector or element (16-byte loads when VEC: H W % 4 == 0, every image base 16-byte aligned --
+ *      checked here --, 4-byte loads otherwise; labels always 8-byte loads), 8-byte stores where two neighbouring pixels of a
+ *      row land on an 8-byte boundary (the 2-pixel padding rules out more), and one thread per grid pixel for the padding.
+ *      GX_EINVAL before any launch: K outside [1, 32], C not 1 or 3, NROW < 1, negative padding, a null source, a destination
+ *      range beyond the atlas, an unknown kind or mode, WORK / ITEMS / VEC that disagree with the rest of the descriptor. */
+#define GX_VIS_COPY 0
+#define GX_VIS_EXP 1
+#define GX_VIS_EXP_MUL 2
+#define GX_VIS_LABEL_COLOUR 3
+#define GX_VIS_ARGMAX_COLOUR 4
+#define GX_VIS_FILL 5
+#define GX_VIS_FP32_CHW 0
+#define GX_VIS_U8_HWC 1
+#define GX_VIS_D_SRC0 0
+#define GX_VIS_D_SRC1 1
+#define GX_VIS_D_STRIDE0 2
+#define GX_VIS_D_STRIDE1 3
+#define GX_VIS_D_DST 4
+#define GX_VIS_D_WORK 5
+#define GX_VIS_D_ITEMS 6
+#define GX_VIS_D_KIND 7
+#define GX_VIS_D_N 8
+#define GX_VIS_D_C 9
+#define GX_VIS_D_H 10
+#define GX_VIS_D_W 11
+#define GX_VIS_D_K 12
+#define GX_VIS_D_NROW 13
+#define GX_VIS_D_PADDING 14
+#define GX_VIS_D_PAD_VALUE 15
+#define GX_VIS_D_MODE 16
+#define GX_VIS_D_VEC 17
+#define GX_VIS_D_PACKED 18
+#define GX_VIS_D_CELL0 19
+#define GX_VIS_D_N_GEOM 20
+#define GX_VIS_D_OWN_PAD 21
+#define GX_VIS_DESC_WORDS 24
+int gx_vis_compose(const long long* table_host, const long long* table_dev, long long table_words, int n_grids,
+                   const unsigned char* palette, int P, float* atlas, long long atlas_words, gx_stream_t stream);
 
 /* ---- FID on the device (scripts/compute_fid.py + third_party/pytorch_fid; genesis_amd/fid.py): pytorch_fid's FID Inception
  *      (Inception-v3, BatchNorm folded into the conv weights by the caller) on NHWC fp32 activations, and the moments of its
