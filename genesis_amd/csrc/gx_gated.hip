@@ -234,6 +234,16 @@ gated_apply_kernel(const float* __restrict__ y, const float* __restrict__ bias, 
     if (amax_parts) gated_block_amax_out(am, amax_parts);      // (uniform)
 }
 
+// dA_h, dA_g as FLOATS, rounded here: the sums pass adds these values up, and the apply pass must subtract S1 / m from the very
+// same values.  With the product left to fuse into that subtraction, a unit whose gradient is exactly 0 (one value per channel:
+// dA - S1 / 1) kept the rounding of dout * sig times rstd gamma -- 1.1e-5 at rstd = 1 / sqrt(eps)
+// (tests/test_step_tail_gpu.py::test_sync_batchnorm_shards[1-1100-1-1-1-*]).
+__device__ __forceinline__ void gated_dA(float vd, float ah, float sg, float* dAh, float* dAg) {
+#pragma clang fp contract(off)
+    *dAh = vd * sg;
+    *dAg = vd * ah * sg * (1.f - sg);
+}
+
 // Backward pass 1: per unit sums  S1 = sum dA, S2 = sum dA * xhat  (dA = gradient w.r.t. the affine-norm output).
 // sums[u] = {S1, S2}.  dA_h = dout * sig;  dA_g = dout * A_h * sig * (1 - sig).
 __global__ void __launch_bounds__(256)
@@ -267,7 +277,8 @@ gated_bwd_sums_kernel(const float* __restrict__ y, const float* __restrict__ bia
             const float xh = ((vh + b_h) - mh) * rh, xg = ((vg + b_g) - mg) * rg;
             const float ah = xh * g_h + be_h, ag = xg * g_g + be_g;
             const float sg = 1.f / (1.f + expf(-ag));
-            const float dAh = vd * sg, dAg = vd * ah * sg * (1.f - sg);
+            float dAh, dAg;
+            gated_dA(vd, ah, sg, &dAh, &dAg);
             acc[0] += (double)dAh; acc[1] += (double)dAh * xh;
             acc[2] += (double)dAg; acc[3] += (double)dAg * xg;
         };
@@ -372,7 +383,8 @@ gated_bwd_apply_kernel(const float* __restrict__ y, const float* __restrict__ bi
                 const float xh = ((vh[e] + b_h) - mh) * rh, xg = ((vg[e] + b_g) - mg) * rg;
                 const float ah = xh * g_h + be_h, ag = xg * g_g + be_g;
                 const float sg = 1.f / (1.f + expf(-ag));
-                const float dAh = vd[e] * sg, dAg = vd[e] * ah * sg * (1.f - sg);
+                float dAh, dAg;
+                gated_dA(vd[e], ah, sg, &dAh, &dAg);
                 float oh = dAh, og = dAg;
                 if (norm != NORM_NONE) {
                     oh = rh * g_h * (dAh - k1h - xh * k2h);
@@ -388,7 +400,8 @@ gated_bwd_apply_kernel(const float* __restrict__ y, const float* __restrict__ bi
         const float xh = ((ph[i] + b_h) - mh) * rh, xg = ((pg[i] + b_g) - mg) * rg;
         const float ah = xh * g_h + be_h, ag = xg * g_g + be_g;
         const float sg = 1.f / (1.f + expf(-ag));
-        const float dAh = pd[i] * sg, dAg = pd[i] * ah * sg * (1.f - sg);
+        float dAh, dAg;
+        gated_dA(pd[i], ah, sg, &dAh, &dAg);
         float oh = dAh, og = dAg;
         if (norm != NORM_NONE) {
             oh = rh * g_h * (dAh - k1h - xh * k2h);

@@ -23,12 +23,27 @@ __device__ __forceinline__ void adam_body(T* __restrict__ p, T* __restrict__ g, 
     const T bc2_sqrt = (T)sqrt(bc2);
     const T one_m_b1 = (T)(1.0 - b1), one_m_b2 = (T)(1.0 - b2), b2_t = (T)b2, eps_t = (T)eps;
     for (size_t i = (size_t)block * blockDim.x + threadIdx.x; i < n; i += (size_t)nblocks * blockDim.x) {
-        const T gi = g[i] * (T)gscale;
+        // Where a product is fused into a sum is WRITTEN here (fma) and nowhere left to the compiler: left to contract as it
+        // pleased, it fused v b2 + (g g)(1 - b2) one way with ZERO_G and the other way without, and the launch the trainer uses
+        // (ZERO_G) differed from gx_adam_step in the last bit of the fp64 v (tests/test_step_tail_gpu.py::test_adam_pair).  The
+        // forms below are the ones the trainer's launch has always computed; gx_adam_step now computes them too.  The fp32 and
+        // the fp64 form differ (and g gscale enters m unrounded but v rounded) for that reason alone: a run continued from a
+        // checkpoint, or compared with an earlier one, keeps its bits.  Neither is more accurate than the other.
+#pragma clang fp contract(off)
+        const T gs = (T)gscale, gr = g[i], mo = m[i];
+        const T gi = gr * gs;
         if (ZERO_G) g[i] = (T)0;                                   // the next iteration accumulates into a clean bucket
-        const T mi = m[i] + (gi - m[i]) * one_m_b1;                // torch: exp_avg.lerp_(grad, 1 - beta1)
-        const T vi = v[i] * b2_t + gi * gi * one_m_b2;             // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+        const T d = fma(gr, gs, -mo);                              // g gscale - m, the product unrounded
+        T mi, vi;
+        if constexpr (sizeof(T) == 4) {
+            mi = mo + d * one_m_b1;                                // torch: exp_avg.lerp_(grad, 1 - beta1)
+            vi = (gi * gi) * one_m_b2 + v[i] * b2_t;               // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+        } else {
+            mi = fma(one_m_b1, d, mo);
+            vi = fma(one_m_b2, gi * gi, b2_t * v[i]);
+        }
         const T denom = sqrt(vi) / bc2_sqrt + eps_t;
-        p[i] = p[i] - step_size * (mi / denom);
+        p[i] = fma(-step_size, mi / denom, p[i]);
         m[i] = mi;
         v[i] = vi;
     }

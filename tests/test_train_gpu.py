@@ -489,7 +489,8 @@ def test_rmsprop_and_sgd_steps_match_torch(kind, tmp_path):
 @pytest.mark.parametrize('kind', ['rmsprop', 'sgd'])
 def test_rmsprop_and_sgd_kernels_match_torch(kind):
     """gx_optimiser_step_pair against torch.optim.RMSprop(lr) / torch.optim.SGD(lr, 0.9) on identical gradients: an fp32 and an
-    fp64 group in one launch, five steps, gradients zeroed as they are consumed."""
+    fp64 group in one launch, five steps, gradients zeroed as they are consumed.  (Group sizes, zero_grads 0, grad_scale
+    and guard bands: test_rmsprop_and_sgd_kernels_on_guarded_groups below.)"""
     import ctypes
     from genesis_amd import _lib
     torch.manual_seed(0)
@@ -512,6 +513,59 @@ def test_rmsprop_and_sgd_kernels_match_torch(kind):
         assert float(gd32.abs().max()) == 0.0 and float(gd64.abs().max()) == 0.0
     np.testing.assert_allclose(d32.cpu().numpy(), refs[0].detach().numpy(), rtol=3e-6, atol=1e-7)
     np.testing.assert_allclose(d64.cpu().numpy(), refs[1].detach().numpy(), rtol=1e-12, atol=1e-14)
+
+
+@pytest.mark.parametrize('n32,n64', [(1, 0), (1023, 1), (1025, 33), (10007, 0), (2048 * 1024 + 1027, 256 * 1024 + 5), (5, 3 * 1024)])
+@pytest.mark.parametrize('kind', ['rmsprop', 'sgd'])
+def test_rmsprop_and_sgd_kernels_on_guarded_groups(kind, n32, n64):
+    """test_rmsprop_and_sgd_kernels_match_torch's launch at the group sizes of tests/test_step_tail_gpu.py::test_adam_pair
+    (step_tail_restatement.PAIR_SIZES), zero_grads 0 / 1 and every grad_scale, two steps each, every buffer between guard bands:
+    p and the state buffer of both groups after every launch against the float64 restatement of that step (fp32: that test's
+    rtol / atol relative to the largest magnitude of the tensor; fp64: its rtol 1e-12 / atol 1e-14), the gradients zeroed or
+    bit-unchanged, the guard bands bit-unchanged, and zero_grads changes no bit of the update."""
+    import ctypes
+    from genesis_amd import _lib
+    from tests import step_tail_restatement as S
+    from tests.test_kernel_edges_gpu import close
+    assert (n32, n64) in S.PAIR_SIZES
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    kind_id, hp, eps, ref_step = (1, 0.99, 1e-8, S.rmsprop_ref) if kind == 'rmsprop' else (2, 0.9, 0.0, S.sgd_ref)
+    step = torch.zeros((), dtype=torch.int64, device=DEV)
+    p32, p64, grads = S.optimiser_inputs(n32, n64, 2, seed=8)
+
+    def run(zero, gs):
+        """-> [(p, state) of the fp32 group, of the fp64 group] after each of the two launches."""
+        b32, b64 = S.GuardedBuffers(n32, torch.float32, 3, DEV, seed=1), S.GuardedBuffers(n64, torch.float64, 3, DEV, seed=2)
+        for b, p0 in ((b32, p32), (b64, p64)):
+            b.views[0].copy_(p0)
+            b.views[2].zero_()
+        v64, kept = (b64.views if n64 else [None] * 3), []
+        for it, (g32, g64) in enumerate(grads):
+            what = 'zero_grads %d grad_scale %g step %d' % (zero, gs, it + 1)
+            b32.views[1].copy_(g32); b64.views[1].copy_(g64)
+            before = [[v.cpu() for v in b.views] for b in (b32, b64)]
+            snaps = [b32.snapshot(), b64.snapshot()]
+            _lib.call('gx_optimiser_step_pair', kind_id, P(b32.views[0]), P(b32.views[1]), P(b32.views[2]), n32,
+                      P(v64[0]), P(v64[1]), P(v64[2]), n64, P(step), 1e-3, hp, eps, gs, zero, st)
+            for b, bf, snap in zip((b32, b64), before, snaps):
+                assert b.guards_unchanged(snap), what
+                if b.n == 0:
+                    continue
+                assert S.same_bits(b.views[1].cpu(), torch.zeros_like(bf[1]) if zero else bf[1]), what + ': gradients'
+                rp, rm = ref_step(bf[0], bf[1], bf[2], gs)
+                if b is b32:
+                    close(b.views[0], rp, 3e-6, 1e-7, what + ': p32')
+                    close(b.views[2], rm, 3e-6, 1e-7, what + ': state32')
+                else:
+                    np.testing.assert_allclose(b.views[0].cpu().numpy(), rp.numpy(), rtol=1e-12, atol=1e-14, err_msg=what)
+                    np.testing.assert_allclose(b.views[2].cpu().numpy(), rm.numpy(), rtol=1e-12, atol=1e-14, err_msg=what)
+                kept.append((b.views[0].clone(), b.views[2].clone()))
+        return kept
+
+    for gs in S.GRAD_SCALES:
+        for (pa, ma), (pb, mb) in zip(run(0, gs), run(1, gs)):
+            assert S.same_bits(pa, pb) and S.same_bits(ma, mb), 'grad_scale %g: zero_grads changed the update' % gs
 
 
 def test_beta_warmup_and_mse_logging():
