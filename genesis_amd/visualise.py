@@ -7,8 +7,8 @@ Every grid of a forward pass is written by ONE gx_vis_compose launch (include/ge
 read in place for exp and argmax, the padding written by the same launch -- and the atlas comes to the host in ONE copy; the
 arrays handed to the writer are views of it (the int64 colour grids: exact conversions of such views).
 
-Not here: add_histogram logging (log_distributions, log_grads_and_weights), a TensorBoard event-file writer, make_grid's
-normalize / scale_each, scripts/visualise_data.py."""
+Not here: a TensorBoard event-file writer, make_grid's normalize / scale_each, scripts/visualise_data.py (add_histogram
+logging: genesis_amd/histogram.py)."""
 import ctypes
 import json
 import os.path as osp

@@ -886,6 +886,47 @@ int gx_seg_metrics(const float* base, long long plane_stride, long long image_st
 int gx_vis_compose(const long long* table_host, const long long* table_dev, long long table_words, int n_grids,
                    const unsigned char* palette, int P, float* atlas, long long atlas_words, gx_stream_t stream);
 
+/* ---- TensorBoard histograms on the device (train.py:313-325 log_distributions, :340-345 log_grads_and_weights: tensorboardX's
+ *      add_histogram = numpy.histogram over a table of edges plus min / max / sum / dot, per tensor on the host;
+ *      genesis_amd/histogram.py).  gx_hist_multi: ONE call histograms n_segments independent segments -- each a contiguous
+ *      device array with its own length and element type -- against one shared edge table.  The descriptors, GX_HIST_DESC_WORDS
+ *      int64 words each, form one table of table_words words that the caller holds twice with the same contents: table_host is
+ *      validated here before anything is launched, table_dev is what the kernels read.  Descriptor words (GX_HIST_D_*):
+ *        SRC    device address, aligned to its element (4 bytes for fp32, 8 for fp64: a slice of a flat buffer is a legal segment;
+ *               16-byte loads from the first 16-byte boundary on, element loads before it and for what is left at the end)
+ *        N      elements, 1 <= N < 2^31;  DTYPE  GX_HIST_FP32 or GX_HIST_FP64
+ *        WORK   first chunk of the segment = sum over the segments before it of ceil(N / GX_HIST_CHUNK); one workgroup per chunk
+ *      edges: fp64 [n_edges] on the device, strictly increasing and finite (the caller's duty: the contents are not read here),
+ *      2 <= n_edges <= GX_HIST_MAX_EDGES.  fp32 values are widened to fp64 and compared with these doubles; a value's bin is found
+ *      by bisection over the table's own entries.  Bin rule (numpy.histogram with explicit edges): bin i holds
+ *      edges[i] <= v < edges[i + 1], the last bin also v == edges[n_edges - 1]; values below the first edge, above the last edge
+ *      and NaN fall in no bin; -0.0 is 0.0.
+ *      Outputs, all written here (nothing needs to be zero beforehand; counts is cleared by a memset node ahead of the launches):
+ *        counts  unsigned [n_segments, n_edges - 1]
+ *        stats   fp64 [n_segments, 4] = (min, max, sum, sum of squares): min and max over the non-NaN values, +-inf included
+ *                (+inf, -inf for a segment of NaNs only), the sums over all non-NaN values in fp64
+ *        tally   uint64 [n_segments, 3] = (NaN count, values below edges[0], values above edges[n_edges - 1])
+ *      ws: gx_hist_multi_ws_bytes(total chunks) bytes, 8-byte aligned: one partial per chunk, added per segment in chunk order by
+ *      a second small launch.  Counts are integer atomics (LDS, then the non-zero bins to memory); the fp64 sums go thread -> wave
+ *      -> workgroup -> segment in a fixed order and through no floating-point atomic, so two calls on the same input return the
+ *      same bits.  When all active lanes of a wave agree on the bin (a zero-filled segment), one lane adds their number.
+ *      GX_EINVAL before any launch: a null pointer, n_segments < 1, n_edges outside [2, GX_HIST_MAX_EDGES], N < 1 or >= 2^31, an
+ *      unknown DTYPE, a SRC that is null or not aligned to its element, WORK that disagrees with the prefix, a table shorter
+ *      than its descriptors, a workspace that is too small. */
+#define GX_HIST_FP32 0
+#define GX_HIST_FP64 1
+#define GX_HIST_D_SRC 0
+#define GX_HIST_D_N 1
+#define GX_HIST_D_DTYPE 2
+#define GX_HIST_D_WORK 3
+#define GX_HIST_DESC_WORDS 4
+#define GX_HIST_CHUNK 8192
+#define GX_HIST_MAX_EDGES 4096
+size_t gx_hist_multi_ws_bytes(long long total_chunks);
+int gx_hist_multi(const long long* table_host, const long long* table_dev, long long table_words, int n_segments,
+                  const double* edges, int n_edges, unsigned int* counts, double* stats, unsigned long long* tally, void* ws,
+                  size_t ws_bytes, gx_stream_t stream);
+
 /* ---- FID on the device (scripts/compute_fid.py + third_party/pytorch_fid; genesis_amd/fid.py): pytorch_fid's FID Inception
  *      (Inception-v3, BatchNorm folded into the conv weights by the caller) on NHWC fp32 activations, and the moments of its
  *      features.  Every output's reduction order is fixed by the layer shape alone (no split-K, no atomics), so an image's
