@@ -225,6 +225,20 @@ def begin_backward():
     torch.autograd.Variable._execution_engine.queue_callback(end_backward)
 
 
+def flat_grad_buffers(grads):
+    """The flat gradient buffers begin_backward built (one per dtype; the padding between two views stays zero) if `grads` are
+    exactly the gradient views of one model in them (a subset would drag the other parameters' gradients along), else None --
+    genesis_amd.clip_grad_norm_ then reduces a few long segments instead of one per parameter."""
+    got = sorted((g.data_ptr(), g.numel()) for g in grads)
+    for book in list(_BOOK.values()):
+        flat = book.get('grads')
+        if flat is None or len(grads) > len(flat[2]):
+            continue
+        if got == sorted((v.data_ptr(), v.numel()) for _, v in flat[2] if v.numel()):
+            return list(flat[1])
+    return None
+
+
 def end_backward():
     st = _STATE
     if not st.in_pass:

@@ -110,7 +110,9 @@ icsbp_fwd_kernel(const float* __restrict__ colour, const double* __restrict__ lo
                 float bv = red_v[0]; int bi = red_i[0];
                 for (int w = 1; w < nw; ++w)
                     if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi)) { bv = red_v[w]; bi = red_i[w]; }
-                idx_sh = bi;
+                // (an image of NaNs only -- a non-finite batch, which TrainStep(skip_nonfinite=True) must survive -- has no
+                //  v > -inf and leaves the sentinel: pixel 0 then, never an address outside the image)
+                idx_sh = (unsigned)bi < (unsigned)HW ? bi : 0;
             }
             __syncthreads();
             best_i = idx_sh;

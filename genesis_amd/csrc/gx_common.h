@@ -57,6 +57,10 @@ struct GxProf {
     ~GxProf() { if (on) gx_prof_end(s); }
 };
 
+// ---- the gradient guard's device record (gx_grad_guard writes it, the guarded tail launches read it; the byte layout is part
+// of the ABI: include/genesis_hip.h, GX_GUARD_R_*) ----
+struct GxGuardRecord { double S; float norm, coef, scale; int ok; long long skipped; };
+
 // ---- deferred parameter-gradient reductions (gx_defer_*; gx_api.cpp owns the queue) ----
 // ca0 / cb0 / CAf / CBf: the record covers the channel block (ca0.., cb0..) of a CAf x CBf weight (CAf == 0: the whole
 // weight, CA x CB) -- the stream-K weight-gradient kernel keeps one slab region per 64 x 64 channel block

@@ -71,6 +71,34 @@ adam_pair_kernel(const AdamGroup a, const AdamGroup b, unsigned nb32, const int6
                                   gscale, blockIdx.x - nb32, gridDim.x - nb32);
 }
 
+// Guarded form (gx_adam_step_pair_guarded): gscale is the gradient guard's `scale` (1/world times the clip coefficient) read from
+// its device record; a record that is not `ok` (a non-finite gradient, err or kl) leaves p, m and v alone and only zeroes the
+// gradients -- the launch and its grid are those of adam_pair_kernel, the body is adam_body itself.
+template <typename T>
+__device__ __forceinline__ void zero_body(T* __restrict__ g, size_t n, unsigned block, unsigned nblocks) {
+    for (size_t i = (size_t)block * blockDim.x + threadIdx.x; i < n; i += (size_t)nblocks * blockDim.x) g[i] = (T)0;
+}
+template <bool ZERO_G>
+__global__ void __launch_bounds__(256)
+adam_pair_guarded_kernel(const AdamGroup a, const AdamGroup b, unsigned nb32, const int64_t* __restrict__ step, double lr,
+                         double b1, double b2, double eps, const GxGuardRecord* __restrict__ rec) {
+    const bool f32 = blockIdx.x < nb32;
+    if (!rec->ok) {
+        if (ZERO_G) {
+            if (f32) zero_body<float>((float*)a.g, a.n, blockIdx.x, nb32);
+            else zero_body<double>((double*)b.g, b.n, blockIdx.x - nb32, gridDim.x - nb32);
+        }
+        return;
+    }
+    const float gscale = rec->scale;
+    if (f32)
+        adam_body<float, ZERO_G>((float*)a.p, (float*)a.g, (float*)a.m, (float*)a.v, a.n, step, lr, b1, b2, eps, gscale,
+                                 blockIdx.x, nb32);
+    else
+        adam_body<double, ZERO_G>((double*)b.p, (double*)b.g, (double*)b.m, (double*)b.v, b.n, step, lr, b1, b2, eps,
+                                  gscale, blockIdx.x - nb32, gridDim.x - nb32);
+}
+
 // torch.optim.RMSprop(lr) defaults (alpha 0.99, eps 1e-8, no momentum, not centred; train.py:171-172) and
 // torch.optim.SGD(lr, momentum 0.9) (train.py:175-176): one state buffer `m` (square average / momentum buffer, zero-initialised:
 // mu * 0 + g reproduces torch's buf = grad at the first step).  KIND 1 = RMSprop, 2 = SGD with momentum.
@@ -98,6 +126,26 @@ simple_opt_pair_kernel(const AdamGroup a, const AdamGroup b, unsigned nb32, int6
                        double eps, float gscale) {
     (void)step;
     if (blockIdx.x < nb32)
+        simple_opt_body<float, KIND, ZERO_G>((float*)a.p, (float*)a.g, (float*)a.m, a.n, lr, hp, eps, gscale, blockIdx.x, nb32);
+    else
+        simple_opt_body<double, KIND, ZERO_G>((double*)b.p, (double*)b.g, (double*)b.m, b.n, lr, hp, eps, gscale,
+                                              blockIdx.x - nb32, gridDim.x - nb32);
+}
+
+template <int KIND, bool ZERO_G>
+__global__ void __launch_bounds__(256)
+simple_opt_pair_guarded_kernel(const AdamGroup a, const AdamGroup b, unsigned nb32, double lr, double hp, double eps,
+                               const GxGuardRecord* __restrict__ rec) {
+    const bool f32 = blockIdx.x < nb32;
+    if (!rec->ok) {
+        if (ZERO_G) {
+            if (f32) zero_body<float>((float*)a.g, a.n, blockIdx.x, nb32);
+            else zero_body<double>((double*)b.g, b.n, blockIdx.x - nb32, gridDim.x - nb32);
+        }
+        return;
+    }
+    const float gscale = rec->scale;
+    if (f32)
         simple_opt_body<float, KIND, ZERO_G>((float*)a.p, (float*)a.g, (float*)a.m, a.n, lr, hp, eps, gscale, blockIdx.x, nb32);
     else
         simple_opt_body<double, KIND, ZERO_G>((double*)b.p, (double*)b.g, (double*)b.m, b.n, lr, hp, eps, gscale,
@@ -192,13 +240,17 @@ philox_noise_kernel(float* __restrict__ u, long long nu, float* __restrict__ z, 
 __global__ void step_inc_kernel(int64_t* step) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *step += 1;
 }
+// guarded: a record that is not `ok` keeps the counter and counts one skipped step instead
+__global__ void step_inc_guarded_kernel(int64_t* step, GxGuardRecord* __restrict__ rec) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (rec->ok) *step += 1; else rec->skipped += 1;
+}
 
 // state = {beta, err_ema, initialised (0/1)}.  err: device scalar (batch-mean reconstruction error of
 // THIS step, already averaged over ranks).  utils/geco.py:39-49.
-__global__ void geco_update_kernel(float* __restrict__ state, const float* __restrict__ err, float goal,
-                                   float step_size, float alpha, float speedup, int use_speedup,
-                                   float beta_min, float beta_max, int64_t* __restrict__ step) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void geco_body(float* __restrict__ state, const float* __restrict__ err, float goal,
+                                          float step_size, float alpha, float speedup, int use_speedup,
+                                          float beta_min, float beta_max, int64_t* __restrict__ step) {
     if (step) *step += 1;          // the optimiser's step counter rides along (gx_geco_update_step)
     const float e = *err;
     float ema = state[1];
@@ -212,6 +264,20 @@ __global__ void geco_update_kernel(float* __restrict__ state, const float* __res
     beta = fminf(fmaxf(beta, beta_min), beta_max);
     state[0] = beta;
     state[1] = ema;
+}
+__global__ void geco_update_kernel(float* __restrict__ state, const float* __restrict__ err, float goal,
+                                   float step_size, float alpha, float speedup, int use_speedup,
+                                   float beta_min, float beta_max, int64_t* __restrict__ step) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    geco_body(state, err, goal, step_size, alpha, speedup, use_speedup, beta_min, beta_max, step);
+}
+// guarded (gx_geco_update_step_guarded): a record that is not `ok` keeps the state and the counter and counts one skipped step
+__global__ void geco_update_guarded_kernel(float* __restrict__ state, const float* __restrict__ err, float goal,
+                                           float step_size, float alpha, float speedup, int use_speedup, float beta_min,
+                                           float beta_max, int64_t* __restrict__ step, GxGuardRecord* __restrict__ rec) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (!rec->ok) { rec->skipped += 1; return; }
+    geco_body(state, err, goal, step_size, alpha, speedup, use_speedup, beta_min, beta_max, step);
 }
 
 }  // namespace
@@ -357,5 +423,86 @@ int gx_adam_step_pair(float* p32, float* g32, float* m32, float* v32, size_t n32
     GX_CHECK_LAUNCH("gx_adam_step_pair");
     return GX_OK;
 }
+
+/* ---- the guarded tail: the same launches with the gradient guard's device record (gx_grad_guard) in place of the host's
+ *      grad_scale.  ok: exactly what the unguarded entry point does when its grad_scale is the record's `scale`; not ok: parameters,
+ *      optimiser state, step counter and GECO state keep their bits, the gradients are still zeroed with zero_grads, and the
+ *      GECO / step-counter launch adds 1 to the record's `skipped`. */
+#define GX_CHECK_RECORD(name) \
+    GX_CHECK_ARG(record && (reinterpret_cast<uintptr_t>(record) & 7) == 0, name ": null or misaligned guard record")
+
+int gx_step_increment_guarded(int64_t* step, void* record, gx_stream_t stream) {
+    GX_CHECK_ARG(step, "gx_step_increment_guarded: null pointer");
+    GX_CHECK_RECORD("gx_step_increment_guarded");
+    hipLaunchKernelGGL(step_inc_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step, (GxGuardRecord*)record);
+    GX_CHECK_LAUNCH("gx_step_increment_guarded");
+    return GX_OK;
+}
+
+int gx_geco_update_step_guarded(float* state, const float* err, float goal, float step_size, float alpha, float speedup,
+                                int use_speedup, float beta_min, float beta_max, int64_t* step, void* record,
+                                gx_stream_t stream) {
+    GX_CHECK_ARG(state && err && step, "gx_geco_update_step_guarded: null pointer");
+    GX_CHECK_RECORD("gx_geco_update_step_guarded");
+    {
+        GxProf pf(KID_GECO, (hipStream_t)stream, 0.0, 24.0);
+        hipLaunchKernelGGL(geco_update_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, err, goal, step_size,
+                           alpha, speedup, use_speedup, beta_min, beta_max, step, (GxGuardRecord*)record);
+    }
+    GX_CHECK_LAUNCH("gx_geco_update_step_guarded");
+    return GX_OK;
+}
+
+int gx_adam_step_pair_guarded(float* p32, float* g32, float* m32, float* v32, size_t n32, double* p64, double* g64,
+                              double* m64, double* v64, size_t n64, int64_t* step, double lr, double beta1, double beta2,
+                              double eps, const void* record, int zero_grads, gx_stream_t stream) {
+    GX_CHECK_ARG(p32 && g32 && m32 && v32 && step && n32 > 0, "gx_adam_step_pair_guarded: null pointer / empty fp32 group");
+    GX_CHECK_ARG(n64 == 0 || (p64 && g64 && m64 && v64), "gx_adam_step_pair_guarded: null fp64 pointer");
+    GX_CHECK_RECORD("gx_adam_step_pair_guarded");
+    hipStream_t s = (hipStream_t)stream;
+    size_t nb32 = (n32 + 1023) / 1024, nb64 = n64 ? (n64 + 1023) / 1024 : 0;
+    if (nb32 > 2048) nb32 = 2048;
+    if (nb64 > 256) nb64 = 256;
+    const AdamGroup a{p32, g32, m32, v32, n32}, b{p64, g64, m64, v64, n64};
+    const GxGuardRecord* rec = (const GxGuardRecord*)record;
+    {
+        GxProf pf(KID_ADAM, s, 0.0, 4.0 * 7.0 * (double)n32 + 8.0 * 7.0 * (double)n64);
+        if (zero_grads)
+            hipLaunchKernelGGL(adam_pair_guarded_kernel<true>, dim3((unsigned)(nb32 + nb64)), dim3(256), 0, s, a, b, (unsigned)nb32,
+                               (const int64_t*)step, lr, beta1, beta2, eps, rec);
+        else
+            hipLaunchKernelGGL(adam_pair_guarded_kernel<false>, dim3((unsigned)(nb32 + nb64)), dim3(256), 0, s, a, b, (unsigned)nb32,
+                               (const int64_t*)step, lr, beta1, beta2, eps, rec);
+    }
+    GX_CHECK_LAUNCH("gx_adam_step_pair_guarded");
+    return GX_OK;
+}
+
+int gx_optimiser_step_pair_guarded(int kind, float* p32, float* g32, float* m32, size_t n32, double* p64, double* g64,
+                                   double* m64, size_t n64, int64_t* step, double lr, double hp, double eps, const void* record,
+                                   int zero_grads, gx_stream_t stream) {
+    (void)step;
+    GX_CHECK_ARG(kind == 1 || kind == 2, "gx_optimiser_step_pair_guarded: kind must be 1 (RMSprop) or 2 (SGD with momentum)");
+    GX_CHECK_ARG(p32 && g32 && m32 && n32 > 0, "gx_optimiser_step_pair_guarded: null pointer / empty fp32 group");
+    GX_CHECK_ARG(n64 == 0 || (p64 && g64 && m64), "gx_optimiser_step_pair_guarded: null fp64 pointer");
+    GX_CHECK_RECORD("gx_optimiser_step_pair_guarded");
+    hipStream_t s = (hipStream_t)stream;
+    size_t nb32 = (n32 + 1023) / 1024, nb64 = n64 ? (n64 + 1023) / 1024 : 0;
+    if (nb32 > 2048) nb32 = 2048;
+    if (nb64 > 256) nb64 = 256;
+    const AdamGroup a{p32, g32, m32, nullptr, n32}, b{p64, g64, m64, nullptr, n64};
+    const dim3 grid((unsigned)(nb32 + nb64));
+    const GxGuardRecord* rec = (const GxGuardRecord*)record;
+    {
+        GxProf pf(KID_ADAM, s, 0.0, 4.0 * 5.0 * (double)n32 + 8.0 * 5.0 * (double)n64);
+#define GX_OPT(K, Z) hipLaunchKernelGGL((simple_opt_pair_guarded_kernel<K, Z>), grid, dim3(256), 0, s, a, b, (unsigned)nb32, lr, hp, eps, rec)
+        if (kind == 1) { if (zero_grads) GX_OPT(1, true); else GX_OPT(1, false); }
+        else { if (zero_grads) GX_OPT(2, true); else GX_OPT(2, false); }
+#undef GX_OPT
+    }
+    GX_CHECK_LAUNCH("gx_optimiser_step_pair_guarded");
+    return GX_OK;
+}
+#undef GX_CHECK_RECORD
 
 }  // extern "C"

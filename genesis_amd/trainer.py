@@ -28,7 +28,7 @@ class TrainStep(object):
     def __init__(self, model, img_size, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, geco=None, use_geco=True,
                  beta_fixed=0.5, process_group=None, graph=False, async_wgrad=False, weight_cache=True, defer_reduces=True,
                  optimiser='adam', beta_warmup=False, train_iter=None, log_mse=False,
-                 materialise_stats=False):
+                 materialise_stats=False, max_grad_norm=None, skip_nonfinite=False):
         """optimiser: 'adam' (torch.optim.Adam(lr); betas / eps as given), 'rmsprop' (torch.optim.RMSprop(lr): alpha 0.99,
         eps 1e-8) or 'sgd' (torch.optim.SGD(lr, 0.9)) -- train.py:170-176.  use_geco=False: the fixed-beta objective
         err + beta_fixed * kl, with beta_warmup the linear ramp beta_fixed * iter / (0.2 * train_iter) of train.py:252-258.
@@ -36,7 +36,17 @@ class TrainStep(object):
         materialise_stats: evaluate, inside every step, the outputs of the forward that a training iteration never reads and
         this build therefore computes on first access (stats.mx_r_k / instance_seg / instance_seg_r,
         genesisv2_config.py:184-188; att_stats.delta) -- the reference's forward computes them unconditionally; a measurement
-        switch (bench.py: value_as_written), nothing consumes the values."""
+        switch (bench.py: value_as_written), nothing consumes the values.
+        max_grad_norm: clip the batch-mean gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_'s coefficient);
+        skip_nonfinite: an iteration whose gradient, err or kl is not finite leaves parameters, optimiser state, step counter and
+        GECO state untouched and is counted in `skipped_steps`.  Either one adds the gradient guard (gx_grad_guard: one streaming
+        reduction, no host read) in front of the guarded forms of the two tail launches; with both off the step issues exactly
+        the launches it always has.  max_grad_norm without skip_nonfinite clips but never skips.  The iteration after a skipped
+        one draws the same noise (it is keyed by the step counter) and module buffers written by the forward pass (BatchNorm
+        running statistics) are not rolled back: INTEGRATION.md section 1."""
+        from .grad_guard import check_max_grad_norm
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         if optimiser not in self.OPTIMISERS:
             raise ValueError('optimiser must be one of %s (train.py:170-176), got %r' % (self.OPTIMISERS, optimiser))
         if beta_warmup and (use_geco and geco is None or geco is not None):
@@ -59,6 +69,12 @@ class TrainStep(object):
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self._flatten()
+        # the gradient guard over the parameters' gradients alone (not the tail scalars, the fp64 triples or the averaged buffers
+        # behind them): table, workspace and record are allocated here, once
+        self._guard = None
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            from .grad_guard import GradGuard
+            self._guard = GradGuard([self.flat_g[:self.n32]] + ([self.flat_g64[:self.n64]] if self.n64 else []))
         # this loop's library context: its deferred-reduction queues, queued weight-gradient jobs, packed-weight cache
         # bookkeeping and step flags are its own (two TrainSteps can coexist in one process)
         self._ctx = int(_lib.load().gx_ctx_create())
@@ -124,6 +140,26 @@ class TrainStep(object):
         if self.geco is not None:
             st.append(self.geco.state)
         return st + list(self.model.buffers())
+
+    def _restorable_state(self):
+        """_train_state plus the guard's record: what a warm-up before a graph capture must put back (its skipped-step count)."""
+        return self._train_state() + ([self._guard.record] if self._guard is not None else [])
+
+    @property
+    def grad_norm(self):
+        """Device fp32 scalar: the global L2 norm of the batch-mean gradient of the last step, before clipping (a view of the
+        guard's record: reading it is the caller's synchronisation).  None without max_grad_norm / skip_nonfinite."""
+        return self._guard.norm if self._guard is not None else None
+
+    @property
+    def clip_coef(self):
+        """Device fp32 scalar: the coefficient the last step's gradient was multiplied by (1 when the norm was below max_grad_norm)."""
+        return self._guard.coef if self._guard is not None else None
+
+    @property
+    def skipped_steps(self):
+        """Device int64 scalar: iterations skipped so far because a gradient, err or kl was not finite (not checkpointed)."""
+        return self._guard.skipped if self._guard is not None else None
 
     def sync_from_rank0(self):
         """Several ranks: every rank starts from rank 0's parameters, optimiser and GECO state and buffers (as
@@ -346,6 +382,8 @@ class TrainStep(object):
         local = fused and gscale == 1.0
         tail = self.bucket.flat_g[self.n32:self.n32 + 2] if gscale == 1.0 else self.bucket.tail(gscale)   # global batch means
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self._guard is not None:
+            return self._update_guarded(tail, gscale, stream, local, fused, beta_used)
         if self.geco is not None:
             self.geco.update(tail[0], step=self.step_t)      # GECO multiplier and the optimiser's step counter: one launch
         else:
@@ -363,6 +401,34 @@ class TrainStep(object):
                       _p(self.flat_p64) if self.n64 else None, _p(self.flat_g64) if self.n64 else None,
                       _p(self.m64) if self.n64 else None, self.n64, _p(self.step_t), self.lr, hp, eps, gscale, 1, stream)
         self._grads_clean = True
+        return self._step_output(tail, gscale, local, fused, beta_used)
+
+    def _update_guarded(self, tail, gscale, stream, local, fused, beta_used):
+        """_update with max_grad_norm / skip_nonfinite: the guard over the (all-reduced) gradients and the raw err / kl of the
+        bucket tail, then the guarded forms of the same two launches, which read the clip scale and the verdict from the guard's
+        device record.  Several ranks reduce the same all-reduced buffer and so take the same decision without another
+        collective."""
+        rec = _p(self._guard.record)
+        self._guard.run(gscale, self.max_grad_norm, check=self.bucket.flat_g[self.n32:self.n32 + 2],
+                        force_ok=not self.skip_nonfinite)
+        if self.geco is not None:
+            self.geco.update(tail[0], step=self.step_t, guard=self._guard.record)
+        else:
+            _lib.call('gx_step_increment_guarded', _p(self.step_t), rec, stream)
+        if self.optimiser == 'adam':
+            _lib.call('gx_adam_step_pair_guarded', _p(self.flat_p), _p(self.flat_g), _p(self.m32), _p(self.v32), self.n32,
+                      _p(self.flat_p64) if self.n64 else None, _p(self.flat_g64) if self.n64 else None,
+                      _p(self.m64) if self.n64 else None, _p(self.v64) if self.n64 else None, self.n64,
+                      _p(self.step_t), self.lr, self.betas[0], self.betas[1], self.eps, rec, 1, stream)
+        else:
+            kind, hp, eps = (1, 0.99, 1e-8) if self.optimiser == 'rmsprop' else (2, 0.9, 0.0)
+            _lib.call('gx_optimiser_step_pair_guarded', kind, _p(self.flat_p), _p(self.flat_g), _p(self.m32), self.n32,
+                      _p(self.flat_p64) if self.n64 else None, _p(self.flat_g64) if self.n64 else None,
+                      _p(self.m64) if self.n64 else None, self.n64, _p(self.step_t), self.lr, hp, eps, rec, 1, stream)
+        self._grads_clean = True
+        return self._step_output(tail, gscale, local, fused, beta_used)
+
+    def _step_output(self, tail, gscale, local, fused, beta_used):
         if local:
             out = beta_used[1:5]                             # ElboFn's (elbo, err, kl, beta used)
         else:
@@ -393,7 +459,7 @@ class TrainStep(object):
         One process: a single graph.  Several ranks: two graphs (forward+backward | GECO+Adam) with the RCCL
         all-reduce of the gradient bucket issued between the two replays -- nothing else runs on the host."""
         self._static_x = x.clone()
-        state = self._train_state()
+        state = self._restorable_state()
         snap = [t.clone() for t in state]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -478,7 +544,7 @@ class TrainStep(object):
         self._follow_level()
         if not self.use_graph or self.graph is not None:
             return
-        state = self._train_state()
+        state = self._restorable_state()
         snap = [t.clone() for t in state]
         iters = self.iters
         self._capture(x)

@@ -405,6 +405,73 @@ int gx_beta_warmup(const int64_t* step, float beta, float warm_iters, float* out
 size_t gx_mse_rmse_ws_bytes(int B);
 int gx_mse_rmse(const float* x, const float* recon, int B, int n, float* out, void* ws, size_t ws_bytes, gx_stream_t stream);
 
+/* ---- gradient guard: clip by global norm and skip non-finite steps without a host read (genesis_amd/grad_guard.py,
+ *      TrainStep(max_grad_norm=, skip_nonfinite=)).  gx_grad_guard: ONE call reduces n_segments gradient segments -- each a
+ *      contiguous device array with its own length, fp32 or fp64 -- to a device record of GX_GUARD_RECORD_BYTES bytes.  The
+ *      descriptor table follows gx_hist_multi's convention: GX_GUARD_DESC_WORDS int64 words per segment, held twice with the same
+ *      contents (table_host is validated before anything is launched, table_dev, 8-byte aligned, is what the kernels read):
+ *        SRC    device address, aligned to its element (4 bytes for fp32, 8 for fp64: a slice of a flat buffer or a lone .grad is
+ *               a legal segment; 16-byte loads from the first 16-byte boundary on, element loads before it and at the end)
+ *        N      elements, 1 <= N < 2^31;  DTYPE  GX_GUARD_FP32 or GX_GUARD_FP64
+ *        WORK   first chunk of the segment = sum over the segments before it of ceil(N / GX_GUARD_CHUNK)
+ *      Arithmetic.  S = sum over all elements of (double)g * (double)g, in fp64 (each product fused into its sum), in a fixed
+ *      order: a grid of min(total chunks, GX_GUARD_MAX_GRID) workgroups walks the chunks with that stride, four accumulators per
+ *      thread -> wave -> workgroup -> one partial per workgroup in ws; a second one-workgroup launch adds the partials in order.
+ *      No floating-point atomic: two calls on the same input write the same bits; ws needs no clearing.
+ *        norm  = (float)((double)gscale * sqrt(S))              gscale: the factor the optimiser launch receives (1 / world)
+ *        coef  = (float)min(1, max_norm / ((double)gscale * sqrt(S) + 1e-6)) with max_norm > 0 (torch.nn.utils.clip_grad_norm_;
+ *                a NaN norm gives a NaN coef, as torch.clamp does), else 1
+ *        scale = gscale * coef, ONE fp32 multiply
+ *        ok    = 1 if force_ok, or if S and every one of the n_check device floats at `check` (0 <= n_check <=
+ *                GX_GUARD_MAX_CHECK; the step's err and kl) are finite; else 0
+ *      The record, 8-byte aligned (byte offsets GX_GUARD_R_*): S fp64 at 0, norm fp32 at 8, coef fp32 at 12, scale fp32 at 16,
+ *      ok int32 at 20, skipped int64 at 24.  gx_grad_guard writes all but `skipped`, a cumulative counter that the caller zeroes
+ *      once and the guarded launches below advance.
+ *      ws: gx_grad_guard_ws_bytes(total chunks) bytes, 8-byte aligned.
+ *      GX_EINVAL before any launch: a null pointer, n_segments < 1, N < 1 or >= 2^31, an unknown DTYPE, a SRC that is null or
+ *      not aligned to its element, WORK that disagrees with the prefix, a table shorter than its descriptors, a misaligned
+ *      table_dev / record / ws, n_check out of range, a workspace that is too small.
+ *      gx_scale_multi_guarded: every element of the segments of such a table times the record's coef, in the element's own type
+ *      (fp64: times (double)coef), in place; coef == 1 returns without reading or writing a gradient.
+ *      The guarded tail: the entry points above with the record's device address in place of the host's grad_scale.  Record ok:
+ *      bit for bit what the unguarded entry point does when its grad_scale is the record's `scale` (and what
+ *      gx_geco_update_step / gx_step_increment do).  Not ok: parameters, every optimiser state buffer, the step counter and the
+ *      GECO state keep their bits; the gradients are still zeroed with zero_grads != 0; gx_geco_update_step_guarded /
+ *      gx_step_increment_guarded -- one of them per step -- adds 1 to `skipped`. */
+#define GX_GUARD_FP32 0
+#define GX_GUARD_FP64 1
+#define GX_GUARD_D_SRC 0
+#define GX_GUARD_D_N 1
+#define GX_GUARD_D_DTYPE 2
+#define GX_GUARD_D_WORK 3
+#define GX_GUARD_DESC_WORDS 4
+#define GX_GUARD_CHUNK 8192
+#define GX_GUARD_MAX_GRID 1024
+#define GX_GUARD_MAX_CHECK 8
+#define GX_GUARD_R_S 0
+#define GX_GUARD_R_NORM 8
+#define GX_GUARD_R_COEF 12
+#define GX_GUARD_R_SCALE 16
+#define GX_GUARD_R_OK 20
+#define GX_GUARD_R_SKIPPED 24
+#define GX_GUARD_RECORD_BYTES 32
+size_t gx_grad_guard_ws_bytes(long long total_chunks);
+int gx_grad_guard(const long long* table_host, const long long* table_dev, long long table_words, int n_segments,
+                  const float* check, int n_check, float gscale, double max_norm, int force_ok, void* record, void* ws,
+                  size_t ws_bytes, gx_stream_t stream);
+int gx_scale_multi_guarded(const long long* table_host, const long long* table_dev, long long table_words, int n_segments,
+                           const void* record, gx_stream_t stream);
+int gx_step_increment_guarded(int64_t* step, void* record, gx_stream_t stream);
+int gx_geco_update_step_guarded(float* state, const float* err, float goal, float step_size, float alpha, float speedup,
+                                int use_speedup, float beta_min, float beta_max, int64_t* step, void* record,
+                                gx_stream_t stream);
+int gx_adam_step_pair_guarded(float* p32, float* g32, float* m32, float* v32, size_t n32, double* p64, double* g64,
+                              double* m64, double* v64, size_t n64, int64_t* step, double lr, double beta1, double beta2,
+                              double eps, const void* record, int zero_grads, gx_stream_t stream);
+int gx_optimiser_step_pair_guarded(int kind, float* p32, float* g32, float* m32, size_t n32, double* p64, double* g64,
+                                   double* m64, size_t n64, int64_t* step, double lr, double hp, double eps, const void* record,
+                                   int zero_grads, gx_stream_t stream);
+
 /* ---- live per-kernel profiling (bench.py's roofline leg): when enabled every kernel launch is bracketed
  *      by two HIP events on its launch stream and tagged with its ALGORITHMIC flops / bytes
  *      (DESIGN.md "kernels and rooflines"); gx_profile_collect accumulates per kernel symbol. */
