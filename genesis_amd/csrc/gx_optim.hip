@@ -152,6 +152,211 @@ simple_opt_pair_guarded_kernel(const AdamGroup a, const AdamGroup b, unsigned nb
                                               blockIdx.x - nb32, gridDim.x - nb32);
 }
 
+// ---- extended forms (gx_adam_step_pair_ex / gx_optimiser_step_pair_ex): the learning rate from a schedule evaluated on the
+//      device from the step counter, an exponential moving average of the parameters, an optional guard record.  The launch and
+//      its grid are those of the kernels above and the arithmetic on p, m, v is adam_body / simple_opt_body itself, called with
+//      the rate this launch computed.
+struct GxSched { int kind; int n_ms; double base, W, s0, T, eta_min, gamma; long long ms[GX_SCHED_MAX_MILESTONES]; const double* lr_dev; };
+struct GxEma { float* e32; double* e64; double decay; int warmup; };
+
+// t = *step after the increment (>= 1), k = t - 1.  The closed forms of torch's SequentialLR([LinearLR, X]) at last_epoch = k, in
+// fp64, every operation in the order genesis_amd/schedule.py: LRSchedule.value writes it (no contraction).  The cosine is HELD at
+// eta_min from j = T on (torch's CosineAnnealingLR is periodic there).
+__device__ __forceinline__ double sched_lr(const GxSched& sc, long long t) {
+#pragma clang fp contract(off)
+    if (sc.kind == GX_SCHED_DEVICE) return *sc.lr_dev;         // the host's own rule: no warm-up factor on top
+    const double k = (double)(t - 1);
+    if (k < sc.W) return sc.base * (sc.s0 + ((1.0 - sc.s0) * k) / sc.W);
+    const double j = k - sc.W;
+    switch (sc.kind) {
+    case GX_SCHED_COSINE: {
+        if (j >= sc.T) return sc.eta_min;
+        return sc.eta_min + ((sc.base - sc.eta_min) * (1.0 + cos((M_PI * j) / sc.T))) / 2.0;
+    }
+    case GX_SCHED_EXPONENTIAL: return sc.base * pow(sc.gamma, j);
+    case GX_SCHED_STEP: {
+        int c = 0;
+        for (int i = 0; i < sc.n_ms; ++i) c += (double)sc.ms[i] <= j ? 1 : 0;
+        return sc.base * pow(sc.gamma, (double)c);
+    }
+    default: return sc.base;
+    }
+}
+
+__device__ __forceinline__ double ema_decay_at(const GxEma& em, long long t) {
+#pragma clang fp contract(off)
+    if (!em.warmup) return em.decay;
+    const double w = (1.0 + (double)t) / (10.0 + (double)t);   // the num_updates rule of tf.train.ExponentialMovingAverage
+    return w < em.decay ? w : em.decay;
+}
+
+// e' = e + w (p' - e), every operation rounded in T: p' is what the optimiser body above just stored from this very thread
+template <typename T>
+__device__ __forceinline__ void ema_body(const T* __restrict__ p, T* __restrict__ e, size_t n, T w, unsigned block,
+                                         unsigned nblocks) {
+    for (size_t i = (size_t)block * blockDim.x + threadIdx.x; i < n; i += (size_t)nblocks * blockDim.x) {
+        // written like adam_body's comment asks: the subtraction and the product-sum are two roundings each, never an fma
+#pragma clang fp contract(off)
+        const T eo = e[i];
+        const T d = p[i] - eo;
+        const T wd = w * d;
+        e[i] = eo + wd;
+    }
+}
+
+// what both _ex kernels do before their body: the verdict, the gradient scale, the rate, the EMA weight, the tail record.
+// -> false: a skipped step (only the gradients are zeroed by the caller)
+__device__ __forceinline__ bool ex_prologue(const GxGuardRecord* __restrict__ rec, const int64_t* __restrict__ step,
+                                            const GxSched& sc, const GxEma& em, float& gscale, double& lr, double& decay_t,
+                                            double* __restrict__ tail) {
+    if (rec) {
+        if (!rec->ok) return false;
+        gscale = rec->scale;
+    }
+    const long long t = (long long)*step;
+    lr = sched_lr(sc, t);
+    decay_t = em.e32 ? ema_decay_at(em, t) : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { tail[0] = lr; tail[1] = decay_t; }
+    return true;
+}
+
+template <bool ZERO_G>
+__global__ void __launch_bounds__(256)
+adam_pair_ex_kernel(const AdamGroup a, const AdamGroup b, unsigned nb32, const int64_t* __restrict__ step, const GxSched sc,
+                    double b1, double b2, double eps, float gscale, const GxGuardRecord* __restrict__ rec, const GxEma em,
+                    double* __restrict__ tail) {
+    const bool f32 = blockIdx.x < nb32;
+    double lr, decay_t;
+    if (!ex_prologue(rec, step, sc, em, gscale, lr, decay_t, tail)) {
+        if (ZERO_G) {
+            if (f32) zero_body<float>((float*)a.g, a.n, blockIdx.x, nb32);
+            else zero_body<double>((double*)b.g, b.n, blockIdx.x - nb32, gridDim.x - nb32);
+        }
+        return;
+    }
+    if (f32) {
+        adam_body<float, ZERO_G>((float*)a.p, (float*)a.g, (float*)a.m, (float*)a.v, a.n, step, lr, b1, b2, eps, gscale,
+                                 blockIdx.x, nb32);
+        if (em.e32) ema_body<float>((const float*)a.p, em.e32, a.n, (float)(1.0 - decay_t), blockIdx.x, nb32);
+    } else {
+        adam_body<double, ZERO_G>((double*)b.p, (double*)b.g, (double*)b.m, (double*)b.v, b.n, step, lr, b1, b2, eps,
+                                  gscale, blockIdx.x - nb32, gridDim.x - nb32);
+        if (em.e32) ema_body<double>((const double*)b.p, em.e64, b.n, 1.0 - decay_t, blockIdx.x - nb32, gridDim.x - nb32);
+    }
+}
+
+template <int KIND, bool ZERO_G>
+__global__ void __launch_bounds__(256)
+simple_opt_pair_ex_kernel(const AdamGroup a, const AdamGroup b, unsigned nb32, const int64_t* __restrict__ step, const GxSched sc,
+                          double hp, double eps, float gscale, const GxGuardRecord* __restrict__ rec, const GxEma em,
+                          double* __restrict__ tail) {
+    const bool f32 = blockIdx.x < nb32;
+    double lr, decay_t;
+    if (!ex_prologue(rec, step, sc, em, gscale, lr, decay_t, tail)) {
+        if (ZERO_G) {
+            if (f32) zero_body<float>((float*)a.g, a.n, blockIdx.x, nb32);
+            else zero_body<double>((double*)b.g, b.n, blockIdx.x - nb32, gridDim.x - nb32);
+        }
+        return;
+    }
+    if (f32) {
+        simple_opt_body<float, KIND, ZERO_G>((float*)a.p, (float*)a.g, (float*)a.m, a.n, lr, hp, eps, gscale, blockIdx.x, nb32);
+        if (em.e32) ema_body<float>((const float*)a.p, em.e32, a.n, (float)(1.0 - decay_t), blockIdx.x, nb32);
+    } else {
+        simple_opt_body<double, KIND, ZERO_G>((double*)b.p, (double*)b.g, (double*)b.m, b.n, lr, hp, eps, gscale,
+                                              blockIdx.x - nb32, gridDim.x - nb32);
+        if (em.e32) ema_body<double>((const double*)b.p, em.e64, b.n, 1.0 - decay_t, blockIdx.x - nb32, gridDim.x - nb32);
+    }
+}
+
+// gx_ema_multi: the same e + w (p - e) over a descriptor table of (p, ema, n, dtype, work offset) segments in chunks of
+// GX_EMA_CHUNK elements, a capped grid walking the chunks with its stride (the table convention of gx_grad_guard)
+__device__ __forceinline__ int ema_segment(const long long* __restrict__ table, int S, long long w) {
+    int lo = 0, hi = S - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[(size_t)mid * GX_EMA_DESC_WORDS + GX_EMA_D_WORK] <= w) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+template <typename T>
+__device__ __forceinline__ void ema_chunk(const T* __restrict__ p, T* __restrict__ e, int n, T w) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+#pragma clang fp contract(off)
+        const T eo = e[i];
+        const T d = p[i] - eo;
+        const T wd = w * d;
+        e[i] = eo + wd;
+    }
+}
+__global__ void __launch_bounds__(256)
+ema_multi_kernel(const long long* __restrict__ table, int S, long long work, const int64_t* __restrict__ step, const GxEma em,
+                 double* __restrict__ decay_used) {
+    const double decay_t = ema_decay_at(em, (long long)*step);
+    if (decay_used && blockIdx.x == 0 && threadIdx.x == 0) *decay_used = decay_t;
+    const double w = 1.0 - decay_t;
+    for (long long c = blockIdx.x; c < work; c += gridDim.x) {
+        const long long* d = table + (size_t)ema_segment(table, S, c) * GX_EMA_DESC_WORDS;
+        const long long N = d[GX_EMA_D_N], first = (c - d[GX_EMA_D_WORK]) * GX_EMA_CHUNK;
+        const int n = (int)(N - first < GX_EMA_CHUNK ? N - first : GX_EMA_CHUNK);
+        if (d[GX_EMA_D_DTYPE] == GX_EMA_FP32)
+            ema_chunk<float>(reinterpret_cast<const float*>(d[GX_EMA_D_SRC]) + first, reinterpret_cast<float*>(d[GX_EMA_D_DST]) + first,
+                             n, (float)w);
+        else
+            ema_chunk<double>(reinterpret_cast<const double*>(d[GX_EMA_D_SRC]) + first,
+                              reinterpret_cast<double*>(d[GX_EMA_D_DST]) + first, n, w);
+    }
+}
+
+// the host's schedule words (GX_SCHED_*) -> the kernel's descriptor; GX_EINVAL-style checks.  -> 0, or the message is set
+int sched_from_words(const char* who, const double* w, const double* lr_dev, GxSched* out) {
+    GX_CHECK_ARG(w, "%s: null schedule descriptor", who);
+    const double kind = w[GX_SCHED_KIND], base = w[GX_SCHED_BASE], W = w[GX_SCHED_WARMUP], s0 = w[GX_SCHED_START];
+    const double T = w[GX_SCHED_T], eta_min = w[GX_SCHED_ETA_MIN], gamma = w[GX_SCHED_GAMMA], nm = w[GX_SCHED_N_MILESTONES];
+    GX_CHECK_ARG(kind == GX_SCHED_CONSTANT || kind == GX_SCHED_COSINE || kind == GX_SCHED_EXPONENTIAL || kind == GX_SCHED_STEP ||
+                 kind == GX_SCHED_DEVICE, "%s: unknown schedule kind %g", who, kind);
+    GX_CHECK_ARG(__builtin_isfinite(base), "%s: the base rate %g is not finite", who, base);
+    GX_CHECK_ARG(W >= 0.0 && W < 9007199254740992.0 && W == (double)(long long)W, "%s: warm-up length W = %g is not a whole number >= 0", who, W);
+    GX_CHECK_ARG(s0 > 0.0 && s0 <= 1.0, "%s: warm-up start factor s0 = %g outside (0, 1]", who, s0);
+    if (kind == GX_SCHED_COSINE) {
+        GX_CHECK_ARG(T > 0.0 && T < 9007199254740992.0 && T == (double)(long long)T, "%s: cosine length T = %g is not a whole number > 0", who, T);
+        GX_CHECK_ARG(__builtin_isfinite(eta_min), "%s: eta_min %g is not finite", who, eta_min);
+    }
+    if (kind == GX_SCHED_EXPONENTIAL || kind == GX_SCHED_STEP)
+        GX_CHECK_ARG(gamma > 0.0 && __builtin_isfinite(gamma), "%s: gamma = %g is not a positive finite number", who, gamma);
+    int n_ms = 0;
+    if (kind == GX_SCHED_STEP) {
+        GX_CHECK_ARG(nm >= 0.0 && nm <= (double)GX_SCHED_MAX_MILESTONES && nm == (double)(int)nm,
+                     "%s: %g milestones, at most %d are held", who, nm, GX_SCHED_MAX_MILESTONES);
+        n_ms = (int)nm;
+        for (int i = 0; i < n_ms; ++i) {
+            const double m = w[GX_SCHED_MILESTONE0 + i];
+            GX_CHECK_ARG(m >= 0.0 && m < 9007199254740992.0 && m == (double)(long long)m, "%s: milestone %d = %g is not a whole number >= 0", who, i, m);
+            GX_CHECK_ARG(i == 0 || m >= w[GX_SCHED_MILESTONE0 + i - 1], "%s: milestones are not in ascending order (milestone %d = %g)", who, i, m);
+        }
+    }
+    GX_CHECK_ARG(kind != GX_SCHED_DEVICE || (lr_dev && (reinterpret_cast<uintptr_t>(lr_dev) & 7) == 0),
+                 "%s: the device schedule needs an 8-byte aligned lr_dev", who);
+    GxSched sc{};
+    sc.kind = (int)kind; sc.n_ms = n_ms; sc.base = base; sc.W = W; sc.s0 = s0; sc.T = T; sc.eta_min = eta_min; sc.gamma = gamma;
+    for (int i = 0; i < n_ms; ++i) sc.ms[i] = (long long)w[GX_SCHED_MILESTONE0 + i];
+    sc.lr_dev = lr_dev;
+    *out = sc;
+    return GX_OK;
+}
+
+int ema_check(const char* who, const float* ema32, const double* ema64, size_t n64, double decay, GxEma* out) {
+    GX_CHECK_ARG(ema32 || !ema64, "%s: ema64 without ema32", who);
+    if (ema32) {
+        GX_CHECK_ARG(n64 == 0 || ema64, "%s: null ema64 with an fp64 group of %zu elements", who, n64);
+        GX_CHECK_ARG((reinterpret_cast<uintptr_t>(ema32) & 3) == 0 && (reinterpret_cast<uintptr_t>(ema64) & 7) == 0,
+                     "%s: an EMA buffer is not aligned to its elements", who);
+        GX_CHECK_ARG(decay >= 0.0 && decay < 1.0, "%s: decay = %g outside [0, 1)", who, decay);
+    }
+    out->e32 = const_cast<float*>(ema32); out->e64 = const_cast<double*>(ema64); out->decay = decay;
+    return GX_OK;
+}
+
 // beta of the fixed-beta objective with linear warm-up (train.py:252-258): beta * iter / (0.2 * train_iter) clamped to
 // [0, beta]; iter = the device step counter BEFORE this iteration's increment
 __global__ void beta_warmup_kernel(const int64_t* __restrict__ step, float beta, float warm_iters, float* __restrict__ out) {
@@ -504,5 +709,109 @@ int gx_optimiser_step_pair_guarded(int kind, float* p32, float* g32, float* m32,
     return GX_OK;
 }
 #undef GX_CHECK_RECORD
+
+/* ---- the extended tail (include/genesis_hip.h): schedule, EMA, optional guard record, tail record -- still one launch */
+#define GX_CHECK_EX(name)                                                                                                       \
+    GX_CHECK_ARG((reinterpret_cast<uintptr_t>(record) & 7) == 0, name ": misaligned guard record");                            \
+    GX_CHECK_ARG(tail && (reinterpret_cast<uintptr_t>(tail) & 7) == 0, name ": null or misaligned tail record");               \
+    GxSched sc;                                                                                                                 \
+    GxEma em{};                                                                                                                 \
+    if (int rc = sched_from_words(name, sched, lr_dev, &sc)) return rc;                                                         \
+    if (int rc = ema_check(name, ema32, ema64, n64, ema_decay, &em)) return rc;                                                 \
+    em.warmup = ema_warmup != 0
+
+int gx_adam_step_pair_ex(float* p32, float* g32, float* m32, float* v32, size_t n32, double* p64, double* g64, double* m64,
+                         double* v64, size_t n64, int64_t* step, const double* sched, const double* lr_dev, double beta1,
+                         double beta2, double eps, float grad_scale, const void* record, float* ema32, double* ema64,
+                         double ema_decay, int ema_warmup, double* tail, int zero_grads, gx_stream_t stream) {
+    GX_CHECK_ARG(p32 && g32 && m32 && v32 && step && n32 > 0, "gx_adam_step_pair_ex: null pointer / empty fp32 group");
+    GX_CHECK_ARG(n64 == 0 || (p64 && g64 && m64 && v64), "gx_adam_step_pair_ex: null fp64 pointer");
+    GX_CHECK_EX("gx_adam_step_pair_ex");
+    hipStream_t s = (hipStream_t)stream;
+    size_t nb32 = (n32 + 1023) / 1024, nb64 = n64 ? (n64 + 1023) / 1024 : 0;
+    if (nb32 > 2048) nb32 = 2048;
+    if (nb64 > 256) nb64 = 256;
+    const AdamGroup a{p32, g32, m32, v32, n32}, b{p64, g64, m64, v64, n64};
+    const GxGuardRecord* rec = (const GxGuardRecord*)record;
+    const double per = em.e32 ? 10.0 : 8.0;                 // read p,g,m,v; write p,m,v,g [; re-read p, read and write the EMA]
+    {
+        GxProf pf(KID_ADAM, s, 0.0, 4.0 * per * (double)n32 + 8.0 * per * (double)n64);
+        if (zero_grads)
+            hipLaunchKernelGGL(adam_pair_ex_kernel<true>, dim3((unsigned)(nb32 + nb64)), dim3(256), 0, s, a, b, (unsigned)nb32,
+                               (const int64_t*)step, sc, beta1, beta2, eps, grad_scale, rec, em, tail);
+        else
+            hipLaunchKernelGGL(adam_pair_ex_kernel<false>, dim3((unsigned)(nb32 + nb64)), dim3(256), 0, s, a, b, (unsigned)nb32,
+                               (const int64_t*)step, sc, beta1, beta2, eps, grad_scale, rec, em, tail);
+    }
+    GX_CHECK_LAUNCH("gx_adam_step_pair_ex");
+    return GX_OK;
+}
+
+int gx_optimiser_step_pair_ex(int kind, float* p32, float* g32, float* m32, size_t n32, double* p64, double* g64, double* m64,
+                              size_t n64, int64_t* step, const double* sched, const double* lr_dev, double hp, double eps,
+                              float grad_scale, const void* record, float* ema32, double* ema64, double ema_decay,
+                              int ema_warmup, double* tail, int zero_grads, gx_stream_t stream) {
+    GX_CHECK_ARG(kind == 1 || kind == 2, "gx_optimiser_step_pair_ex: kind must be 1 (RMSprop) or 2 (SGD with momentum)");
+    GX_CHECK_ARG(p32 && g32 && m32 && step && n32 > 0, "gx_optimiser_step_pair_ex: null pointer / empty fp32 group");
+    GX_CHECK_ARG(n64 == 0 || (p64 && g64 && m64), "gx_optimiser_step_pair_ex: null fp64 pointer");
+    GX_CHECK_EX("gx_optimiser_step_pair_ex");
+    hipStream_t s = (hipStream_t)stream;
+    size_t nb32 = (n32 + 1023) / 1024, nb64 = n64 ? (n64 + 1023) / 1024 : 0;
+    if (nb32 > 2048) nb32 = 2048;
+    if (nb64 > 256) nb64 = 256;
+    const AdamGroup a{p32, g32, m32, nullptr, n32}, b{p64, g64, m64, nullptr, n64};
+    const dim3 grid((unsigned)(nb32 + nb64));
+    const GxGuardRecord* rec = (const GxGuardRecord*)record;
+    const double per = em.e32 ? 8.0 : 6.0;
+    {
+        GxProf pf(KID_ADAM, s, 0.0, 4.0 * per * (double)n32 + 8.0 * per * (double)n64);
+#define GX_OPT(K, Z) hipLaunchKernelGGL((simple_opt_pair_ex_kernel<K, Z>), grid, dim3(256), 0, s, a, b, (unsigned)nb32, \
+                                        (const int64_t*)step, sc, hp, eps, grad_scale, rec, em, tail)
+        if (kind == 1) { if (zero_grads) GX_OPT(1, true); else GX_OPT(1, false); }
+        else { if (zero_grads) GX_OPT(2, true); else GX_OPT(2, false); }
+#undef GX_OPT
+    }
+    GX_CHECK_LAUNCH("gx_optimiser_step_pair_ex");
+    return GX_OK;
+}
+#undef GX_CHECK_EX
+
+int gx_ema_multi(const long long* table_host, const long long* table_dev, long long table_words, int n_segments,
+                 const int64_t* step, double decay, int warmup, double* decay_used, gx_stream_t stream) {
+    const char* who = "gx_ema_multi";
+    GX_CHECK_ARG(table_host && table_dev, "%s: null descriptor table", who);
+    GX_CHECK_ARG(n_segments >= 1, "%s: n_segments = %d below 1", who, n_segments);
+    GX_CHECK_ARG(table_words >= (long long)n_segments * GX_EMA_DESC_WORDS, "%s: %d segments do not fit a table of %lld words", who,
+                 n_segments, table_words);
+    GX_CHECK_ARG((reinterpret_cast<uintptr_t>(table_dev) & 7) == 0, "%s: the device table must be 8-byte aligned", who);
+    GX_CHECK_ARG(step && (reinterpret_cast<uintptr_t>(step) & 7) == 0, "%s: null or misaligned step counter", who);
+    GX_CHECK_ARG((reinterpret_cast<uintptr_t>(decay_used) & 7) == 0, "%s: misaligned decay_used", who);
+    GX_CHECK_ARG(decay >= 0.0 && decay < 1.0, "%s: decay = %g outside [0, 1)", who, decay);
+    long long work = 0;
+    double bytes = 0.0;
+    for (int si = 0; si < n_segments; ++si) {
+        const long long* d = table_host + (size_t)si * GX_EMA_DESC_WORDS;
+        const long long N = d[GX_EMA_D_N], dtype = d[GX_EMA_D_DTYPE];
+        const uintptr_t src = (uintptr_t)d[GX_EMA_D_SRC], dst = (uintptr_t)d[GX_EMA_D_DST];
+        GX_CHECK_ARG(dtype == GX_EMA_FP32 || dtype == GX_EMA_FP64, "%s: segment %d: unknown dtype %lld", who, si, dtype);
+        GX_CHECK_ARG(N >= 1 && N < (1LL << 31), "%s: segment %d: N = %lld outside [1, 2^31)", who, si, N);
+        GX_CHECK_ARG(src && dst, "%s: segment %d: null source or destination", who, si);
+        GX_CHECK_ARG(((src | dst) & (dtype == GX_EMA_FP32 ? 3 : 7)) == 0, "%s: segment %d: source %#llx or destination %#llx is not aligned to its %d-byte elements",
+                     who, si, (unsigned long long)src, (unsigned long long)dst, dtype == GX_EMA_FP32 ? 4 : 8);
+        GX_CHECK_ARG(d[GX_EMA_D_WORK] == work, "%s: segment %d: WORK = %lld, the prefix is %lld", who, si, d[GX_EMA_D_WORK], work);
+        work += (N + GX_EMA_CHUNK - 1) / GX_EMA_CHUNK;
+        bytes += (double)N * (dtype == GX_EMA_FP32 ? 4 : 8);
+    }
+    GX_CHECK_ARG(work < (1LL << 31), "%s: %lld chunks are too many for one launch", who, work);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned grid = (unsigned)(work < GX_EMA_MAX_GRID ? work : GX_EMA_MAX_GRID);
+    GxEma em{nullptr, nullptr, decay, warmup != 0};
+    {
+        GxProf pf(KID_ADAM, s, 0.0, 3.0 * bytes);
+        hipLaunchKernelGGL(ema_multi_kernel, dim3(grid), dim3(256), 0, s, table_dev, n_segments, work, step, em, decay_used);
+    }
+    GX_CHECK_LAUNCH("gx_ema_multi");
+    return GX_OK;
+}
 
 }  // extern "C"

@@ -28,7 +28,8 @@ class TrainStep(object):
     def __init__(self, model, img_size, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, geco=None, use_geco=True,
                  beta_fixed=0.5, process_group=None, graph=False, async_wgrad=False, weight_cache=True, defer_reduces=True,
                  optimiser='adam', beta_warmup=False, train_iter=None, log_mse=False,
-                 materialise_stats=False, max_grad_norm=None, skip_nonfinite=False):
+                 materialise_stats=False, max_grad_norm=None, skip_nonfinite=False, lr_schedule=None, ema_decay=None,
+                 ema_warmup=False):
         """optimiser: 'adam' (torch.optim.Adam(lr); betas / eps as given), 'rmsprop' (torch.optim.RMSprop(lr): alpha 0.99,
         eps 1e-8) or 'sgd' (torch.optim.SGD(lr, 0.9)) -- train.py:170-176.  use_geco=False: the fixed-beta objective
         err + beta_fixed * kl, with beta_warmup the linear ramp beta_fixed * iter / (0.2 * train_iter) of train.py:252-258.
@@ -43,10 +44,23 @@ class TrainStep(object):
         reduction, no host read) in front of the guarded forms of the two tail launches; with both off the step issues exactly
         the launches it always has.  max_grad_norm without skip_nonfinite clips but never skips.  The iteration after a skipped
         one draws the same noise (it is keyed by the step counter) and module buffers written by the forward pass (BatchNorm
-        running statistics) are not rolled back: INTEGRATION.md section 1."""
+        running statistics) are not rolled back: INTEGRATION.md section 1.
+        lr_schedule: a genesis_amd.schedule.LRSchedule; `lr` is its base rate and the optimiser launch computes the rate of every
+        step on the device from the step counter, so a captured graph follows the schedule (`current_lr`; kind='device': `set_lr`).
+        ema_decay: keep an exponential moving average of the parameters, updated inside the same launch (ema_warmup: the decay is
+        min(ema_decay, (1 + t) / (10 + t))); `ema_weights()`, `ema_state_dict()`, `ema_decay_used`.  A skipped step advances
+        neither.  With all three at their defaults the step issues exactly the launches it always has."""
         from .grad_guard import check_max_grad_norm
+        from .schedule import LRSchedule, check_ema_decay
         self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError('lr_schedule must be a genesis_amd.schedule.LRSchedule (or None), got %r' % (lr_schedule,))
+        self.ema_decay = check_ema_decay(ema_decay)
+        if ema_warmup and self.ema_decay is None:
+            raise ValueError('ema_warmup needs ema_decay')
+        self.lr_schedule, self.ema_warmup = lr_schedule, bool(ema_warmup)
+        self._ex = lr_schedule is not None or self.ema_decay is not None      # the _ex form of the optimiser launch
         if optimiser not in self.OPTIMISERS:
             raise ValueError('optimiser must be one of %s (train.py:170-176), got %r' % (self.OPTIMISERS, optimiser))
         if beta_warmup and (use_geco and geco is None or geco is not None):
@@ -75,6 +89,18 @@ class TrainStep(object):
         if self.max_grad_norm is not None or self.skip_nonfinite:
             from .grad_guard import GradGuard
             self._guard = GradGuard([self.flat_g[:self.n32]] + ([self.flat_g64[:self.n64]] if self.n64 else []))
+        # schedule / averaged weights: the EMA buffers (laid out like the flat parameters, starting as a copy of them), the device
+        # tail record (lr used, decay used) and the device rate of the 'device' kind, allocated here, once
+        self.ema32 = self.ema64 = self._tail = self._lr_dev = self._sched_words = None
+        self._in_ema = False
+        if self._ex:
+            from . import schedule as _sched
+            self._sched = self.lr_schedule if self.lr_schedule is not None else _sched.LRSchedule('constant')
+            self._sched_base = None
+            self._tail = torch.zeros(_sched.TAIL_BYTES // 8, dtype=torch.float64, device=self.device)
+            self._lr_dev = torch.full((), float(lr), dtype=torch.float64, device=self.device)
+            if self.ema_decay is not None:
+                self.ema32, self.ema64 = self.flat_p.clone(), self.flat_p64.clone()
         # this loop's library context: its deferred-reduction queues, queued weight-gradient jobs, packed-weight cache
         # bookkeeping and step flags are its own (two TrainSteps can coexist in one process)
         self._ctx = int(_lib.load().gx_ctx_create())
@@ -139,6 +165,8 @@ class TrainStep(object):
         st = [self.flat_p, self.flat_p64, self.m32, self.v32, self.m64, self.v64, self.step_t]
         if self.geco is not None:
             st.append(self.geco.state)
+        if self._ex:           # the averaged weights, the tail record (current_lr) and the device rate travel with the parameters
+            st += [t for t in (self.ema32, self.ema64, self._tail, self._lr_dev) if t is not None]
         return st + list(self.model.buffers())
 
     def _restorable_state(self):
@@ -389,7 +417,9 @@ class TrainStep(object):
         else:
             _lib.call('gx_step_increment', _p(self.step_t), stream)
         # fp32 and fp64 parameter groups in one launch; it zeroes the gradients it consumed
-        if self.optimiser == 'adam':
+        if self._ex:
+            self._optimiser_ex(gscale, None, stream)
+        elif self.optimiser == 'adam':
             _lib.call('gx_adam_step_pair', _p(self.flat_p), _p(self.flat_g), _p(self.m32), _p(self.v32), self.n32,
                       _p(self.flat_p64) if self.n64 else None, _p(self.flat_g64) if self.n64 else None,
                       _p(self.m64) if self.n64 else None, _p(self.v64) if self.n64 else None, self.n64,
@@ -415,7 +445,9 @@ class TrainStep(object):
             self.geco.update(tail[0], step=self.step_t, guard=self._guard.record)
         else:
             _lib.call('gx_step_increment_guarded', _p(self.step_t), rec, stream)
-        if self.optimiser == 'adam':
+        if self._ex:
+            self._optimiser_ex(1.0, rec, stream)
+        elif self.optimiser == 'adam':
             _lib.call('gx_adam_step_pair_guarded', _p(self.flat_p), _p(self.flat_g), _p(self.m32), _p(self.v32), self.n32,
                       _p(self.flat_p64) if self.n64 else None, _p(self.flat_g64) if self.n64 else None,
                       _p(self.m64) if self.n64 else None, _p(self.v64) if self.n64 else None, self.n64,
@@ -427,6 +459,89 @@ class TrainStep(object):
                       _p(self.m64) if self.n64 else None, self.n64, _p(self.step_t), self.lr, hp, eps, rec, 1, stream)
         self._grads_clean = True
         return self._step_output(tail, gscale, local, fused, beta_used)
+
+    def _optimiser_ex(self, gscale, rec, stream):
+        """The optimiser launch in its _ex form (lr_schedule / ema_decay): still one launch.  rec: the guard's record or None."""
+        if self._sched_words is None or self._sched_base != self.lr:
+            self._sched_words, self._sched_base = self._sched.words(self.lr), self.lr      # (host words, copied by the call)
+        n64 = self.n64
+        p64, g64, m64, v64 = ((_p(t) if n64 else None) for t in (self.flat_p64, self.flat_g64, self.m64, self.v64))
+        ema = self.ema32 is not None
+        tail_args = (rec, _p(self.ema32) if ema else None, _p(self.ema64) if ema and n64 else None,
+                     self.ema_decay if ema else 0.0, int(self.ema_warmup), _p(self._tail), 1, stream)
+        sched = ctypes.c_void_p(self._sched_words.ctypes.data)
+        if self.optimiser == 'adam':
+            _lib.call('gx_adam_step_pair_ex', _p(self.flat_p), _p(self.flat_g), _p(self.m32), _p(self.v32), self.n32, p64, g64, m64,
+                      v64, n64, _p(self.step_t), sched, _p(self._lr_dev), self.betas[0], self.betas[1], self.eps, gscale, *tail_args)
+        else:
+            kind, hp, eps = (1, 0.99, 1e-8) if self.optimiser == 'rmsprop' else (2, 0.9, 0.0)
+            _lib.call('gx_optimiser_step_pair_ex', kind, _p(self.flat_p), _p(self.flat_g), _p(self.m32), self.n32, p64, g64, m64,
+                      n64, _p(self.step_t), sched, _p(self._lr_dev), hp, eps, gscale, *tail_args)
+
+    @property
+    def current_lr(self):
+        """Device fp64 scalar: the learning rate the last step that was not skipped used (a view of the tail record: reading it is
+        the caller's synchronisation).  None without lr_schedule / ema_decay."""
+        return self._tail[0] if self._ex else None
+
+    @property
+    def ema_decay_used(self):
+        """Device fp64 scalar: the EMA decay of the last step that was not skipped (ema_warmup: below ema_decay early on).  None
+        without ema_decay."""
+        return self._tail[1] if self.ema32 is not None else None
+
+    def set_lr(self, value):
+        """kind='device' only: the rate the following steps use, written to the device scalar the launch reads -- a captured graph
+        stays as it is."""
+        if not self._ex or self._sched.kind != 'device':
+            raise _lib.GenesisHipError("set_lr needs lr_schedule=LRSchedule('device'); assign .lr for a base rate (re-captures)")
+        value = float(value)
+        if value != value or value in (float('inf'), float('-inf')):
+            raise ValueError('set_lr: the rate must be finite, got %r' % (value,))
+        self._lr_dev.fill_(value)
+
+    def _ema_swap(self):
+        with torch.no_grad():
+            for p, e in ((self.flat_p, self.ema32), (self.flat_p64, self.ema64)):
+                tmp = p.clone()
+                p.copy_(e)
+                e.copy_(tmp)
+
+    def ema_weights(self):
+        """Context manager: inside, the model's parameters hold the averaged weights (contents swapped on the device, the tensors
+        and every captured graph stay); on exit -- also on an exception -- they are swapped back.  Module buffers (BatchNorm running
+        statistics) are the live ones.  step() inside raises."""
+        import contextlib
+        if self.ema32 is None:
+            raise _lib.GenesisHipError('ema_weights needs TrainStep(ema_decay=)')
+
+        @contextlib.contextmanager
+        def swapped():
+            if self._in_ema:
+                raise _lib.GenesisHipError('ema_weights is not re-entrant')
+            self._ema_swap()
+            self._in_ema = True
+            try:
+                yield self.model
+            finally:
+                self._in_ema = False
+                self._ema_swap()
+        return swapped()
+
+    def _ema_slice(self, p):
+        is64, off, n = self.bucket.slot[id(p)]
+        return (self.ema64 if is64 else self.ema32)[off:off + n].view(p.shape)
+
+    def ema_state_dict(self):
+        """A state dict shaped like the model's, of clones: every parameter is its average, every buffer the live one (BatchNorm
+        running statistics are not averaged)."""
+        if self.ema32 is None:
+            raise _lib.GenesisHipError('ema_state_dict needs TrainStep(ema_decay=)')
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for name, p in self.model.named_parameters():
+            # (inside ema_weights() the contents are swapped: the parameter itself holds the average)
+            sd[name] = (p if self._in_ema else self._ema_slice(p)).detach().clone()
+        return type(self.model.state_dict())(sd)
 
     def _step_output(self, tail, gscale, local, fused, beta_used):
         if local:
@@ -591,6 +706,8 @@ class TrainStep(object):
         forward_kwargs (rand_pixel / eps / seed_idx injection, parity tests) force the eager path.  After a change of the
         matmul precision level or the tap-conv mode the next call re-records the weight cache and, with graph=True, re-captures
         the step."""
+        if self._in_ema:
+            raise _lib.GenesisHipError('step() inside ema_weights(): the parameters hold the averaged weights; leave the block first')
         self._follow_level()
         if self.use_graph and not forward_kwargs:
             if self.graph is None:
@@ -616,6 +733,8 @@ class TrainStep(object):
         """The reference's checkpoint dict (train.py:405-420): `optimiser_state_dict` is a genuine
         torch.optim.Adam state_dict over model.parameters() in order (exp_avg / exp_avg_sq / step per parameter), so
         a checkpoint written here resumes in the reference's loop (train.py:179-207) and vice versa."""
+        if self._in_ema:
+            raise _lib.GenesisHipError('state_dict() inside ema_weights(): the parameters hold the averaged weights; leave the block first')
         params = list(self.model.parameters())
         step = int(self.step_t)
         if self.optimiser == 'adam':
@@ -633,14 +752,26 @@ class TrainStep(object):
                     opt.state[p] = {'step': torch.tensor(float(step)), 'square_avg': m.clone()}
                 else:
                     opt.state[p] = {'momentum_buffer': m.clone()}
-        return {'model_state_dict': self.model.state_dict(),
-                'optimiser_state_dict': opt.state_dict(),
+        osd = opt.state_dict()
+        extra = {}
+        if self.lr_schedule is not None:
+            # what torch's schedulers leave in the optimiser: 'lr' = the rate the NEXT step uses, 'initial_lr' = the base rate
+            g0 = osd['param_groups'][0]
+            g0['initial_lr'] = self.lr
+            g0['lr'] = float(self._lr_dev) if self._sched.kind == 'device' else self._sched.value(step, self.lr)
+            extra['lr_schedule'] = self._sched.state_dict()
+        if self.ema32 is not None:
+            extra['ema_state_dict'] = self.ema_state_dict()
+        ckpt = {'model_state_dict': self.model.state_dict(),
+                'optimiser_state_dict': osd,
                 # (fixed-beta objective with the warm-up ramp: the ramp value of iteration `iter_idx`, the `beta` that
                 #  train.py:252-258 computed in the iteration whose end save_checkpoint records)
                 'beta': self.geco.beta.detach().clone() if self.geco is not None else self._current_fixed_beta(iter_idx),
                 'err_ema': (self.geco.err_ema.detach().clone() if self.geco.err_ema is not None else None)
                 if self.geco is not None else None,
                 'iter_idx': iter_idx}
+        ckpt.update(extra)          # (nothing without lr_schedule / ema_decay: the reference's keys and no others)
+        return ckpt
 
     def _current_fixed_beta(self, iter_idx):
         if not self.beta_warmup:
@@ -687,7 +818,18 @@ class TrainStep(object):
             # (torch.optim.SGD keeps no step count: the iteration index of the checkpoint stands in)
             self.step_t.fill_(steps.pop() if steps else (int(ckpt.get('iter_idx', -1)) + 1 if self.optimiser == 'sgd' else 0))
         g0 = osd['param_groups'][0]
-        self.lr = g0['lr']
+        # (a checkpoint written under a scheduler, torch's or this loop's: 'lr' is the next step's rate, 'initial_lr' the base)
+        self.lr = g0.get('initial_lr', g0['lr']) if self.lr_schedule is not None else g0['lr']
+        if self._ex:
+            with torch.no_grad():
+                self._lr_dev.fill_(float(g0['lr']))
+                if self.ema32 is not None:
+                    # the averaged weights of the checkpoint; one without them: the average starts from the loaded parameters
+                    esd = ckpt.get('ema_state_dict')
+                    self.ema32.copy_(self.flat_p); self.ema64.copy_(self.flat_p64)
+                    if esd is not None:
+                        for name, p in self.model.named_parameters():
+                            self._ema_slice(p).copy_(esd[name])
         if self.optimiser == 'adam':
             self.betas, self.eps = tuple(g0['betas']), g0['eps']
         if self.geco is not None:

@@ -472,6 +472,81 @@ int gx_optimiser_step_pair_guarded(int kind, float* p32, float* g32, float* m32,
                                    double* m64, size_t n64, int64_t* step, double lr, double hp, double eps, const void* record,
                                    int zero_grads, gx_stream_t stream);
 
+/* ---- learning-rate schedules and averaged weights in the optimiser launch (genesis_amd/schedule.py, genesis_amd/ema.py,
+ *      TrainStep(lr_schedule=, ema_decay=, ema_warmup=)).  gx_adam_step_pair_ex / gx_optimiser_step_pair_ex: the grid, the
+ *      fp32 + fp64 split, zero_grads and the arithmetic on p, m, v of gx_adam_step_pair / gx_optimiser_step_pair, with the
+ *      learning rate computed ON THE DEVICE from the step counter, so a captured HIP graph follows a schedule without being
+ *      captured again.  The plain entry points are untouched: a caller that does not opt in keeps its launches and its bits.
+ *      record: NULL = the unguarded form (the gradient times grad_scale); else the gradient guard's record: ok = the gradient
+ *        times the record's `scale` (grad_scale is ignored); not ok = ONLY the gradients are zeroed (with zero_grads): p, m, v, the
+ *        EMA and the tail record keep their bits.
+ *      sched: GX_SCHED_WORDS fp64 words in HOST memory, read during the call (constants of the launch: fine inside a graph).
+ *        With t = *step after the increment (>= 1), k = t - 1, base = word BASE, W = WARMUP (0: none), s0 = START in (0, 1]:
+ *          k < W:   lr = base (s0 + (1 - s0) k / W)
+ *          else, j = k - W, by KIND:
+ *            GX_SCHED_CONSTANT     lr = base
+ *            GX_SCHED_COSINE       lr = eta_min + (base - eta_min)(1 + cos(pi j / T)) / 2 for j < T, eta_min from j = T on.
+ *                                  The rate is HELD there; torch's CosineAnnealingLR is periodic and climbs again.
+ *            GX_SCHED_EXPONENTIAL  lr = base gamma^j
+ *            GX_SCHED_STEP         lr = base gamma^(number of milestones <= j); at most GX_SCHED_MAX_MILESTONES, ascending
+ *            GX_SCHED_DEVICE       lr = *lr_dev, an fp64 device scalar the host may write between steps; no warm-up factor
+ *        -- the closed forms of torch's SequentialLR([LinearLR(s0, 1, W), X], [W]) at last_epoch = k, evaluated in fp64 in every
+ *        workgroup (cos / pow: a few ulp of fp64).
+ *      ema32 / ema64: NULL (both) = no average; else buffers laid out like p32 / p64, updated after p' is formed as
+ *        d = p' - e; e' = e + w d, each operation rounded in the parameter's own type (no fma), w = (T)(1 - decay_t) with
+ *        decay_t = ema_decay, or min(ema_decay, (1 + t) / (10 + t)) with ema_warmup != 0, formed in fp64.  The average is kept in
+ *        the parameter's type (as torch.optim.swa_utils.AveragedModel and timm keep it).
+ *      tail: two fp64 device words, 8-byte aligned, written by one thread of a step that is not skipped: the lr used at byte
+ *        GX_TAIL_LR and decay_t (0 without an EMA) at byte GX_TAIL_DECAY.
+ *      gx_ema_multi: the same e + w (p - e) for an unchanged loop (torch's own optimiser): one launch over a host + device table
+ *        of n_segments x GX_EMA_DESC_WORDS int64 words (SRC: the parameter, DST: its average, N elements, DTYPE GX_EMA_FP32 /
+ *        GX_EMA_FP64, WORK: first chunk = sum over the segments before it of ceil(N / GX_EMA_CHUNK)), a grid of at most
+ *        GX_EMA_MAX_GRID workgroups; t is read from the device counter `step` (bump it with gx_step_increment first);
+ *        decay_used: NULL, or an fp64 device word that receives decay_t.
+ *      GX_EINVAL before any launch: a null group with n > 0 (a null ema64 with n64 > 0 when ema32 is given), a null step, a null
+ *      or misaligned tail, ema_decay outside [0, 1), an unknown KIND, W < 0, T <= 0 (cosine), gamma <= 0 (exponential, step), more
+ *      than GX_SCHED_MAX_MILESTONES milestones or unsorted ones, s0 outside (0, 1], GX_SCHED_DEVICE with a null lr_dev, a base
+ *      rate that is not finite; for the table what gx_grad_guard refuses, for SRC and DST alike. */
+#define GX_SCHED_CONSTANT 0
+#define GX_SCHED_COSINE 1
+#define GX_SCHED_EXPONENTIAL 2
+#define GX_SCHED_STEP 3
+#define GX_SCHED_DEVICE 4
+#define GX_SCHED_KIND 0
+#define GX_SCHED_BASE 1
+#define GX_SCHED_WARMUP 2
+#define GX_SCHED_START 3
+#define GX_SCHED_T 4
+#define GX_SCHED_ETA_MIN 5
+#define GX_SCHED_GAMMA 6
+#define GX_SCHED_N_MILESTONES 7
+#define GX_SCHED_MILESTONE0 8
+#define GX_SCHED_MAX_MILESTONES 8
+#define GX_SCHED_WORDS 16
+#define GX_TAIL_LR 0
+#define GX_TAIL_DECAY 8
+#define GX_TAIL_BYTES 16
+#define GX_EMA_FP32 0
+#define GX_EMA_FP64 1
+#define GX_EMA_D_SRC 0
+#define GX_EMA_D_DST 1
+#define GX_EMA_D_N 2
+#define GX_EMA_D_DTYPE 3
+#define GX_EMA_D_WORK 4
+#define GX_EMA_DESC_WORDS 5
+#define GX_EMA_CHUNK 8192
+#define GX_EMA_MAX_GRID 1024
+int gx_adam_step_pair_ex(float* p32, float* g32, float* m32, float* v32, size_t n32, double* p64, double* g64, double* m64,
+                         double* v64, size_t n64, int64_t* step, const double* sched, const double* lr_dev, double beta1,
+                         double beta2, double eps, float grad_scale, const void* record, float* ema32, double* ema64,
+                         double ema_decay, int ema_warmup, double* tail, int zero_grads, gx_stream_t stream);
+int gx_optimiser_step_pair_ex(int kind, float* p32, float* g32, float* m32, size_t n32, double* p64, double* g64, double* m64,
+                              size_t n64, int64_t* step, const double* sched, const double* lr_dev, double hp, double eps,
+                              float grad_scale, const void* record, float* ema32, double* ema64, double ema_decay,
+                              int ema_warmup, double* tail, int zero_grads, gx_stream_t stream);
+int gx_ema_multi(const long long* table_host, const long long* table_dev, long long table_words, int n_segments,
+                 const int64_t* step, double decay, int warmup, double* decay_used, gx_stream_t stream);
+
 /* ---- live per-kernel profiling (bench.py's roofline leg): when enabled every kernel launch is bracketed
  *      by two HIP events on its launch stream and tagged with its ALGORITHMIC flops / bytes
  *      (DESIGN.md "kernels and rooflines"); gx_profile_collect accumulates per kernel symbol. */
