@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "../../include/genesis_hip.h"
+#include "gx_pack.h"
 
 // ---- error plumbing: C ABI never throws; negative return + thread-local message ----
 void gx_set_error(const char* fmt, ...);
@@ -126,71 +127,21 @@ __device__ __forceinline__ float gx_wave_max(float v) {
     return v;
 }
 
-// ---- Winograd F(2x2,3x3) weight operand (gx_wino.hip; also produced by the packed-weight cache of gx_conv.hip) ----
-// (G g G^T)[xi][nu], p = 4 xi + nu, for output channel m / reduction channel k.  mode 0: g = w[m][k] (forward);
-// mode 1: g = w[k][m] rotated by 180 degrees (data gradient).  w is [Co][Ci][3][3].
-__device__ __forceinline__ float gx_wino_u_value(const float* __restrict__ w, int mode, int Co, int Ci, int m, int k,
-                                                 int p) {
-    const int Mact = mode == 0 ? Co : Ci, Kact = mode == 0 ? Ci : Co;
-    if (m >= Mact || k >= Kact) return 0.f;
-    const int xi = p >> 2, nu = p & 3;
-    float t[3];   // row xi of G g
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        float g0, g1, g2;
-        if (mode == 0) {
-            const float* q = w + ((size_t)m * Ci + k) * 9 + b;
-            g0 = q[0]; g1 = q[3]; g2 = q[6];
-        } else {
-            const float* q = w + ((size_t)k * Ci + m) * 9 + (2 - b);
-            g0 = q[6]; g1 = q[3]; g2 = q[0];
-        }
-        t[b] = xi == 0 ? g0 : (xi == 1 ? 0.5f * (g0 + g1 + g2) : (xi == 2 ? 0.5f * (g0 - g1 + g2) : g2));
-    }
-    return nu == 0 ? t[0] : (nu == 1 ? 0.5f * (t[0] + t[1] + t[2]) : (nu == 2 ? 0.5f * (t[0] - t[1] + t[2]) : t[2]));
-}
-// position of U(p, k, m) in the conv kernel's operand order:
-// [m tile][chunk of 8 k][position][lane = 32 ((k >> 2) & 1) + (m & 31)][2 (k & 3) + ((m >> 5) & 1)]
-// (lane half h of the chunk's MFMA j multiplies channel 4 h + j: the B operand's four values are one 16-byte LDS read)
-__host__ __device__ __forceinline__ size_t gx_wino_u_slot(int m, int k, int p, int Kpad) {
-    const size_t base = ((size_t)(m >> 6) * (Kpad >> 3) + (k >> 3)) * 16 + p;
-    return base * 512 + (size_t)((((((k >> 2) & 1) << 5) | (m & 31)) << 3) | ((k & 3) << 1) | ((m >> 5) & 1));
-}
-// The same operands for the bf16 matrix pipe (gx_wino.hip: wino_conv_h_kernel): every U value as three bf16 pieces, chunks of 16
-// reduction channels.  32-bit word (two channels k even, k + 1) of piece `piece` of position p:
-// [m tile 64][chunk k >> 4][position 16][piece 3][m half (m >> 5) & 1][lane = 32 ((k >> 3) & 1) + (m & 31)][(k & 7) >> 1]
-// -- a wave's A operand of (position, piece, m half) is 1 KB, lane-linear: one 16-byte load per lane.
-// (NP = 1: the one-piece form, gx_wino_precision(3) -- one bf16 piece per value, positions 2 KB apart instead of 6 KB)
-__host__ __device__ __forceinline__ size_t gx_wino_h_word(int m, int k, int p, int piece, int Kpad16, int NP = 3) {
-    return ((((((size_t)(m >> 6) * (Kpad16 >> 4) + (k >> 4)) * 16 + p) * NP + piece) * 2 + ((m >> 5) & 1)) * 256) +
-           (size_t)((((k >> 3) & 1) * 32 + (m & 31)) * 4 + ((k & 7) >> 1));
-}
+// ---- Winograd F(2x2,3x3) conv3x3 (gx_wino.hip); the weight operand and its layouts: gx_pack.h ----
 __host__ __device__ __forceinline__ size_t gx_wino_h_bytes(int Kpad16, int Mpad) {
     return (size_t)(Mpad >> 6) * (Kpad16 >> 4) * 16 * 6144;
 }
 bool gx_wino_h_on();     // Winograd layers on the bf16 pipe (default; gx_wino_precision(0) / GENESIS_WINO_BF16X6=0: fp32 pipe)
 bool gx_conv_input_hint(const float** p0, int* n0, const float** p1, int* n1);      // the armed gx_conv_input_amax hint (gx_wino.hip), not cleared
-bool gx_wino_f16_pending(void);   // ... and the NEXT launch of this thread on two fp16 pieces per operand (gx_conv_input_amax armed): pack kinds 45 / 46
-bool gx_wino_b1_on(void);         // ... on ONE bf16 piece per operand (gx_wino_precision(3)): pack kinds 65 / 66
+bool gx_wino_f16_pending(void);   // ... and the NEXT launch of this thread on two fp16 pieces per operand (gx_conv_input_amax armed): the Winograd views in GX_FORM_F16X2
+bool gx_wino_b1_on(void);         // ... on ONE bf16 piece per operand (gx_wino_precision(3)): the Winograd views in GX_FORM_BF16X1
 // conv with an already packed U (16 * Kpad * Mpad floats; bf16 pipe: gx_wino_h_bytes): out[N,M,H,W] from in[N,K,H,W]
 bool gx_wino_eligible(int N, int K, int M, int H, int W);
 int gx_wino_launch(const float* in, const float* U, float* out, int N, int K, int M, int H, int W, hipStream_t s);
 
 
 // ---- k-quad tap convolutions (gx_kq.hip): 16-byte k-contiguous MFMA operand reads for the chip-filling layers ----
-// packed-weight layout [m tile 64][chunk of 8 k][tap, phase-major][quad (k >> 2) & 1][m & 63][k & 3]
-// tap order: the [t] order of gx_conv.hip's packs, except the transposed conv's data gradient (25 taps, t = kh*5+kw),
-// whose taps are grouped by parity plane (kh & 1, kw & 1): planes of 9, 6, 6, 4 taps, (kh / 2, kw / 2) row-major inside
-__host__ __device__ __forceinline__ int gx_kq_dg_tap_slot(int t) {
-    const int kh = t / 5, kw = t % 5;
-    const int pa = kh & 1, pb = kw & 1;
-    const int p = pa * 2 + pb;
-    const int base = p == 0 ? 0 : (p == 1 ? 9 : (p == 2 ? 15 : 21));
-    return base + (kh >> 1) * (3 - pb) + (kw >> 1);
-}
-__host__ __device__ __forceinline__ size_t gx_kq_w_slot(int m, int k, int tslot, int NT, int Kpad) {
-    return ((((size_t)(m >> 6) * (Kpad >> 3) + (k >> 3)) * NT + tslot) * 2 + ((k >> 2) & 1)) * 256 + (m & 63) * 4 + (k & 3);
-}
+// (packed-weight layouts: gx_pack.h)
 bool gx_kq_c3_eligible(int N, int K, int M, int H, int W);
 bool gx_kq_deconv_eligible(int N, int K, int M, int Hb, int Wb, int mult);   // mult: workgroups per (pixel, channel) tile
 int gx_kq_c3_launch(const float* in, const float* wp, const float* bias, int act, float* out, int N, int K, int M, int H,
@@ -199,18 +150,16 @@ int gx_kq_deconv_fwd_launch(const float* in, const float* wp0, const float* wp1,
                             int K, int M, int Hb, int Wb, float* stats, int* stats_parts, hipStream_t s);
 int gx_kq_deconv_dgrad_launch(const float* dy, const float* wp, float* dx, int N, int K, int M, int Hb, int Wb,
                               hipStream_t s);
-// ... on the bf16 matrix pipe: weights packed by kinds 22 / 23 = [channel tile][16-channel chunk][tap][piece hi|mid|lo]
+// ... on the bf16 matrix pipe: weights packed as GX_VIEW_DT_ROW0 / _ROW1 in GX_FORM_BF16X3 = [channel tile][16-channel chunk][tap][piece hi|mid|lo]
 // [octet][64 output channels][8 channels] in bf16 (two per 32-bit word)
 bool gx_kq_deconv_h_eligible(int N, int K, int M, int Hb, int Wb);
-size_t gx_kq_deconv_h_pack_bytes(int K, int M, int nt);
 // ... or from THREE fp16 piece products (gx_kq_precision(2), DESIGN.md finding 40): x * 2^e = hi + lo (11 + 11 significant bits),
-// hi*hi + hi*lo + lo*hi; e per TENSOR from its largest magnitude so that the pieces sit inside fp16's exponent range.  Pack kinds
-// 40 / 41 / 42 / 43 / 44 / 47 / 48 = 20 / 21 / 22 / 23 / 24 / 27 / 28 as two fp16 pieces of w * 2^e (two piece slots per tap); the weight tensor's amax lives in the last
-// 64 bytes of the packing's slack (written by the amax launch that precedes the pack, read by the pack and by the conv kernels).
+// hi*hi + hi*lo + lo*hi; e per TENSOR from its largest magnitude so that the pieces sit inside fp16's exponent range.  The weights
+// are packed in GX_FORM_F16X2: two fp16 pieces of w * 2^e (two piece slots per tap), the weight tensor's amax in the packing's
+// trailer (gx_pack.h).
 bool gx_kq_f16_on();
-// ... or from ONE bf16 piece per operand (gx_kq_precision(3)): packs 60 .. 68 = 20 .. 28 as one bf16 piece (round to nearest even)
+// ... or from ONE bf16 piece per operand (gx_kq_precision(3)): the weights packed in GX_FORM_BF16X1
 bool gx_kq_b1_on();
-__host__ __device__ __forceinline__ bool gx_pack_f16(int pack) { return pack >= 40 && pack < 60; }
 // GENESIS_MATMUL_PRECISION (gx_api.cpp): -1 unset, else the level 0 highest / 1 high / 2 medium -- read by every family's default
 // ahead of its own variables; gx_matmul_level_mode: the family mode of a level (0 -> 0, 1 -> 2, 2 -> 3)
 int gx_env_matmul_level(void);
@@ -218,15 +167,6 @@ inline int gx_matmul_level_mode(int level) { return level == 0 ? 0 : (level == 1
 int gx_kq_mode_now(void);         // the resolved mode of each family (gx_matmul_precision)
 int gx_wgq_mode_now(void);
 int gx_wino_mode_now(void);
-__host__ __device__ __forceinline__ size_t gx_kq_h_amax_off(int K, int M, int nt) {      // byte offset of that float
-    return (size_t)((M + 63) / 64) * (K / 16) * nt * 6144 + 16384 - 64;
-}
-__host__ __device__ __forceinline__ int gx_f16_scale_exp(float amax) {     // amax * 2^e in [2^14, 2^15); 0 / inf / nan: e = 0
-    if (!(amax > 0.f) || amax > 3.0e38f) return 0;
-    int ex;
-    (void)frexpf(amax, &ex);
-    return 15 - ex;
-}
 // amax of a tensor (n floats) as kAmaxParts partial maxima in ws (gx_kq_amax_ws_floats() floats, 16-byte aligned): one launch; the
 // conv kernels reduce the partials themselves
 constexpr int kAmaxParts = 256;
@@ -312,33 +252,24 @@ __device__ __forceinline__ void gx_block_amax_store(float am, float* __restrict_
 }
 #endif
 int gx_kq_weight_amax_launch(const float* w, int n, float* out, hipStream_t s);          // one workgroup (weights are small)
-bool gx_kq_deconv_dgrad_h_eligible(int N, int K, int M, int Hb, int Wb);      // pack 24: all 25 taps, plane-major slots
+bool gx_kq_deconv_dgrad_h_eligible(int N, int K, int M, int Hb, int Wb);      // GX_VIEW_DT_DGRAD: all 25 taps, plane-major slots
 int gx_kq_deconv_dgrad_h_launch(const float* dy, const float* wp, float* dx, int N, int K, int M, int Hb, int Wb,
                                 hipStream_t s, float* amax_ws = nullptr, const float* w_amax = nullptr,
                                 const float* x_parts = nullptr, int x_nparts = 0);     // x_parts: the input's partial maxima from its producer
 int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp1, const float* bias, float* out, int N,
                               int K, int M, int Hb, int Wb, float* stats, int* stats_parts, hipStream_t s,
-                              float* amax_ws = nullptr, const float* w_amax = nullptr,    // amax_ws != NULL: the fp16 x 3 form (packs 42 / 43)
+                              float* amax_ws = nullptr, const float* w_amax = nullptr,    // amax_ws != NULL: the fp16 x 3 form (GX_FORM_F16X2)
                               const float* x_parts = nullptr, int x_nparts = 0);
-// 32-bit word of element (m, k even, k + 1) of piece `piece` of tap t
-// ... kinds 20 / 21 (conv3x3 forward / data gradient of <= 32-output-channel layers): 32 output channels per channel tile
-// (NP: pieces per value -- 3 bf16 ones, or 2 fp16 ones in the packs 40 - 48 of the fp16 x 3 form)
-__host__ __device__ __forceinline__ size_t gx_kq_h32_word(int m, int k, int t, int piece, int NT, int K, int NP = 3) {
-    return ((((size_t)(m >> 5) * (K >> 4) + (k >> 4)) * NT + t) * NP + piece) * 256 + (((k >> 3) & 1) * 32 + (m & 31)) * 4 + ((k & 7) >> 1);
-}
 bool gx_kq_c3h_eligible(int N, int K, int M, int H, int W);
 int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int act, float* out, int N, int K, int M, int H,
                      int W, hipStream_t s, const float* mask = nullptr, int mask_act = 0, float* amax_ws = nullptr,
-                     const float* w_amax = nullptr);         // amax_ws != NULL: the fp16 x 3 form (packs 40 / 41)
-// 5 x 5 stride-1 conv on the bf16 pipe (pack kinds 27 / 28 = the bf16-piece forms of 7 / 8; K a multiple of 16, H and W of 16)
+                     const float* w_amax = nullptr);         // amax_ws != NULL: the fp16 x 3 form (GX_FORM_F16X2)
+// 5 x 5 stride-1 conv on the bf16 pipe (GX_VIEW_C5 / _C5_FLIP in the 16-bit-pipe forms; K a multiple of 16, H and W of 16)
 bool gx_kq_c5h_eligible(int N, int K, int M, int H, int W);
 int gx_chan_sums_launch(const float* x, int N, int C, int HW, float* part, float* out, hipStream_t s);   // gx_misc.hip
 int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K, int M, int H, int W, hipStream_t s,
                      float* amax_ws = nullptr, const float* w_amax = nullptr, const float* x_parts = nullptr,
-                     int x_nparts = 0);      // (packs 47 / 48; x_parts: the input's partial maxima, gx_kq_amax_link)
-__host__ __device__ __forceinline__ size_t gx_kq_h_word(int m, int k, int t, int piece, int NT, int K, int NP = 3) {
-    return ((((size_t)(m >> 6) * (K >> 4) + (k >> 4)) * NT + t) * NP + piece) * 512 + (((k >> 3) & 1) * 64 + (m & 63)) * 4 + ((k & 7) >> 1);
-}
+                     int x_nparts = 0);      // (x_parts: the input's partial maxima, gx_kq_amax_link)
 
 // ---- second-generation weight gradients (gx_wgq.hip): LDS-DMA staging of both operands, grouped launches -------------
 bool gx_wgq_c3_eligible(int N, int Cin, int Cout, int H, int W);

@@ -28,7 +28,7 @@
 // what the stated fp32 parity tolerance of the path needs (no bf16/xf32 shortcuts).
 // The one opt-in exception is gx_tapconv_precision(3) (include/genesis_hip.h): the tap-conv kernels then take one bf16 piece per
 // operand -- one v_mfma_f32_32x32x16_bf16 per pair of taps x 8 channels (TapPairs), fp32 accumulation, weights packed as one bf16
-// plane (kinds 70 ..).  The weight-gradient kernels of this file stay on the fp32 pipe in every mode.
+// plane (GX_FORM_TAP_BF16X1).  The weight-gradient kernels of this file stay on the fp32 pipe in every mode.
 #include "gx_common.h"
 
 #include <cstdio>
@@ -246,7 +246,7 @@ __device__ __forceinline__ void tapconv_body(const float* __restrict__ in, const
     if constexpr (B1) {
     // ---- one bf16 piece per operand: 8-channel chunks, LDS stage = input [CHS][8 ch] + weights [NT][64 m][8 ch], all bf16 (16 bytes
     // per halo position / per (tap, channel)).  The input is converted once, between the register prefetch and its ds_write (so this
-    // form stages through registers whatever the DMA choice); the weights arrive packed (kinds 70 ..: [t][k / 8][m][8 ch] bf16).
+    // form stages through registers whatever the DMA choice); the weights arrive packed (GX_FORM_TAP_BF16X1: [t][k / 8][m][8 ch] bf16).
     constexpr int NWB = (NT * 64 + 255) / 256;        // 16-byte weight vectors per thread per chunk
     constexpr TapPairs<MODE> TP{};
     const int BUFB = 16 * (CHS + 64 * NT);            // bytes per pipeline stage
@@ -650,111 +650,23 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, const float
 }
 
 // ------------------------------------------------------------------ weight packing
-// Wp[t][k][m] (k padded to Kpad, m padded to Mpad, zero filled).
-//   pack 0: conv3x3 fwd    W[co][ci][3][3]  -> m=co, k=ci, t=kh*3+kw
-//   pack 1: conv3x3 dgrad  W[co][ci][3][3]  -> m=ci, k=co, t=(kh,kw) reads W[..][2-kh][2-kw]
-//   pack 2/3: deconv fwd rows a=0/1, W[ci][co][5][5] -> m=co, k=ci, t=khi*5+kw, kh=2*khi+a
-//   pack 4: deconv dgrad   W[ci][co][5][5]  -> m=ci, k=co, t=kh*5+kw
-__device__ __forceinline__ float pack_weight_value(const float* __restrict__ w, int pack, int Co, int Ci, int m,
-                                                   int k, int t) {
-    float v = 0.f;
-    if (pack >= 10) pack -= 10;
-    if (pack == 0) {
-        if (m < Co && k < Ci) v = w[((size_t)m * Ci + k) * 9 + t];
-    } else if (pack == 1) {
-        if (m < Ci && k < Co) v = w[((size_t)k * Ci + m) * 9 + (8 - t)];
-    } else if (pack == 2 || pack == 3) {
-        const int kh = 2 * (t / 5) + (pack - 2), kw = t % 5;
-        if (m < Co && k < Ci) v = w[((size_t)k * Co + m) * 25 + kh * 5 + kw];
-    } else if (pack == 4) {
-        if (m < Ci && k < Co) v = w[((size_t)m * Co + k) * 25 + t];
-    } else if (pack == 7) {   // 5x5 stride 1, cross-correlation: w [Co = M][Ci = K][5][5]
-        if (m < Co && k < Ci) v = w[((size_t)m * Ci + k) * 25 + t];
-    } else if (pack == 8) {   // 5x5 stride 1, true convolution with the channel roles swapped: w [Co = K][Ci = M][5][5]
-        if (k < Co && m < Ci) v = w[((size_t)k * Ci + m) * 25 + (24 - t)];
-    } else {   // 5 / 6: Winograd operands of the conv3x3 forward / data gradient (t = position)
-        v = gx_wino_u_value(w, pack - 5, Co, Ci, m, k, t);
-    }
-    return v;
-}
-// destination of element (t, k, m): [t][k][m] for the tap-conv kernels, the operand order of gx_wino.hip for packs 5 / 6,
-// the k-quad order of gx_kq.hip for packs 10..14 (= packs 0..4 in that layout)
-__device__ __forceinline__ size_t pack_dest(int pack, int idx, int m, int k, int t, int Kpad, int NT) {
-    if (pack >= 10) return gx_kq_w_slot(m, k, pack == 14 ? gx_kq_dg_tap_slot(t) : t, NT, Kpad);
-    return (pack == 5 || pack == 6) ? gx_wino_u_slot(m, k, t, Kpad) : (size_t)idx;
-}
-
-// packs 25 / 26 (= 5 / 6: the Winograd operands for gx_wino.hip's bf16-pipe kernel), 20 / 21 (= 0 / 1, gx_kq.hip's Q_C3H) and 22 / 23 / 24 (= 2 / 3 / 4 for the bf16 matrix pipe, gx_kq.hip's QCfgDTH / Q_DGH): every weight as three bf16 pieces, two
-// channels per 32-bit word -- the thread of an even k writes the three words of (k, k + 1), the odd one nothing
-// packs 42 / 43 / 44: 22 / 23 / 24 as TWO fp16 pieces of w * 2^f16_exp (gx_kq.hip's fp16 x 3 form; f16_exp from the tensor's amax)
-// packs 60 .. 68: 20 .. 28 as ONE bf16 piece, w rounded to nearest even (the one-piece form, gx_matmul_precision(2))
-__device__ __forceinline__ void pack_h_store(const float* __restrict__ w, float* __restrict__ wp, int pack, int Co, int Ci,
-                                             int m, int k, int t, int NT, int Kpad, int f16_exp = 0) {
-    if (k & 1) return;
-    const bool f16 = gx_pack_f16(pack), b1 = pack >= 60;
-    if (f16) pack -= 20;
-    if (b1) pack -= 40;
-    unsigned wd[3];
-    float v[2] = {pack_weight_value(w, pack - 20, Co, Ci, m, k, t), pack_weight_value(w, pack - 20, Co, Ci, m, k + 1, t)};
-    unsigned short pc[2][3];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        if (b1) {
-            pc[e][0] = __builtin_bit_cast(unsigned short, (__bf16)v[e]);
-            pc[e][1] = pc[e][2] = 0;
-            continue;
-        }
-        if (f16) {
-            const float ws = ldexpf(v[e], f16_exp);
-            const _Float16 h = (_Float16)ws;
-            pc[e][0] = __builtin_bit_cast(unsigned short, h);
-            pc[e][1] = __builtin_bit_cast(unsigned short, (_Float16)(ws - (float)h));
-            pc[e][2] = 0;
-            continue;
-        }
-        const __bf16 h = (__bf16)v[e];
-        const float r1 = v[e] - (float)h;
-        const __bf16 mm = (__bf16)r1;
-        const __bf16 l = (__bf16)(r1 - (float)mm);
-        pc[e][0] = __builtin_bit_cast(unsigned short, h);
-        pc[e][1] = __builtin_bit_cast(unsigned short, mm);
-        pc[e][2] = __builtin_bit_cast(unsigned short, l);
-    }
-    const int np = b1 ? 1 : (f16 ? 2 : 3);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        if (q >= np) break;
-        wd[q] = (unsigned)pc[0][q] | ((unsigned)pc[1][q] << 16);
-        const size_t dst = pack <= 21 ? gx_kq_h32_word(m, k, t, q, NT, Kpad, np)       // 20 / 21: conv3x3, 32-channel tiles
-                           : ((pack == 25 || pack == 26) ? gx_wino_h_word(m, k, t, q, Kpad, b1 ? 1 : 3)   // 25 / 26: Winograd operands (= 5 / 6), t = position; 27 / 28: 5 x 5 stride 1 (= 7 / 8)
-                                         : gx_kq_h_word(m, k, pack == 24 ? gx_kq_dg_tap_slot(t) : t, q, NT, Kpad, np));
-        wp[dst] = __builtin_bit_cast(float, wd[q]);
-    }
-}
-
-// packs 70 .. 74, 77, 78: 0 .. 4, 7, 8 (the tap-conv kernels' weights) as ONE bf16 piece, w rounded to nearest even, for the
-// one-bf16 form of tapconv_body (gx_tapconv_precision(3)): [t][k / 8][m][8 ch] -- the 8 channels of (t, m) are one 16-byte vector,
-// a lane's A operand.  The thread of an even k writes the word of (k, k + 1), the odd one nothing.  NT * Kpad * Mpad * 2 bytes.
-__device__ __forceinline__ void pack_b1_store(const float* __restrict__ w, float* __restrict__ wp, int pack, int Co, int Ci,
-                                              int m, int k, int t, int Kpad, int Mpad) {
-    if (k & 1) return;
-    pack -= 70;
-    const unsigned wd = tap_pk_bf16(pack_weight_value(w, pack, Co, Ci, m, k, t), pack_weight_value(w, pack, Co, Ci, m, k + 1, t));
-    reinterpret_cast<unsigned*>(wp)[(((size_t)t * (Kpad >> 3) + (k >> 3)) * Mpad + m) * 4 + ((k & 7) >> 1)] = wd;
-}
-
-__global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ wp, int pack,
-                                    int Co, int Ci, int NT, int Kpad, int Mpad) {
-    const int total = NT * Kpad * Mpad;
-    const int f16_exp = gx_pack_f16(pack) ? gx_f16_scale_exp(((pack == 45 || pack == 46) ? 2.25f : 1.f) * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(wp) + gx_kq_h_amax_off(Kpad, Mpad, NT))) : 0;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+// Wp(t, k, m) of a GxPack (gx_pack.h: the views, the forms, who reads them), k padded to Kpad, m to Mpad, zero filled.
+// Elements [begin, end) of the padded range, every `step`-th from this thread's first: the one loop of both pack kernels.
+__device__ __forceinline__ void pack_elements(const float* __restrict__ w, float* __restrict__ wp, GxPack pack, int Co, int Ci,
+                                              int Kpad, int Mpad, int begin, int end, int step) {
+    const int f16_exp = gx_pack_scale_exp(pack, wp, Kpad, Mpad);
+    for (int idx = begin; idx < end; idx += step) {
         const int m = idx % Mpad;
         const int k = (idx / Mpad) % Kpad;
         const int t = idx / (Mpad * Kpad);
-        if (pack >= 70) { pack_b1_store(w, wp, pack, Co, Ci, m, k, t, Kpad, Mpad); continue; }
-        if (pack >= 20) { pack_h_store(w, wp, pack, Co, Ci, m, k, t, NT, Kpad, f16_exp); continue; }
-        wp[pack_dest(pack, idx, m, k, t, Kpad, NT)] = pack_weight_value(w, pack, Co, Ci, m, k, t);
+        gx_pack_store(w, wp, pack, Co, Ci, m, k, t, Kpad, Mpad, f16_exp);
     }
+}
+
+__global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ wp, GxPack pack, int Co, int Ci, int Kpad,
+                                    int Mpad) {
+    pack_elements(w, wp, pack, Co, Ci, Kpad, Mpad, blockIdx.x * blockDim.x + threadIdx.x, gx_pack_taps(pack.view) * Kpad * Mpad,
+                  gridDim.x * blockDim.x);
 }
 
 // ------------------------------------------------------------------ weight gradients
@@ -1554,7 +1466,7 @@ struct TapPlan {
     size_t lds_bytes;
     size_t out_elems;  // N*M*Ho*Wo
     dim3 grid;
-    bool b1;           // the one-bf16 form (gx_tapconv_precision(3)): 8-channel chunks, packs 70 ..
+    bool b1;           // the one-bf16 form (gx_tapconv_precision(3)): 8-channel chunks, GX_FORM_TAP_BF16X1
 };
 
 template <int MODE>
@@ -1711,8 +1623,11 @@ int launch_splitk_reduce(const float* part, const float* bias, float* out, const
 // start of an iteration and the conv entry points are served from the cache until gx_weight_cache_release().
 struct PackEntry {
     const float* w; float* wp;
-    int pack, Co, Ci, NT, Kpad, Mpad;
+    GxPack pack;
+    int Co, Ci, Kpad, Mpad;
     int chunk0;             // first workgroup (chunk of kPackChunk elements) of this entry in the batched launch
+    int total() const { return gx_pack_taps(pack.view) * Kpad * Mpad; }     // elements of the padded range
+    bool is(const float* w_, GxPack p, int Co_, int Ci_) const { return w == w_ && pack == p && Co == Co_ && Ci == Ci_; }
 };
 constexpr int kPackChunk = 2048;
 struct PackCache {
@@ -1727,67 +1642,77 @@ std::mutex g_cache_mutex;
 #define g_cache_recording (gx_ctx_flags().cache_recording)   // cache id being recorded by this context, or -1
 #define g_cache_active (gx_ctx_flags().cache_active)         // cache id this context's conv calls are served from, or -1
 
-// the fp16 x 3 packs' (kinds >= 40) weight tensors: largest magnitude -> the packing's trailer; one workgroup per cache entry (the
-// others return at once); 3 x 3 (kinds 40 / 41) or 5 x 5 weights: Co * Ci * 9 | 25 floats
+// the fp16 form's weight tensors: largest magnitude -> the packing's trailer; one workgroup per cache entry (the others return
+// at once)
 __global__ void __launch_bounds__(1024)
 pack_amax_batch_kernel(const PackEntry* __restrict__ entries) {
     const PackEntry e = entries[blockIdx.x];
-    if (!gx_pack_f16(e.pack)) return;
-    const float r = gx_wg1024_amax(e.w, e.Co * e.Ci * ((e.pack <= 41 || e.pack == 45 || e.pack == 46) ? 9 : 25));
-    if (threadIdx.x == 0) *reinterpret_cast<float*>(reinterpret_cast<char*>(e.wp) + gx_kq_h_amax_off(e.Kpad, e.Mpad, e.NT)) = r;
+    if (!gx_pack_has_trailer(e.pack.form)) return;
+    const float r = gx_wg1024_amax(e.w, e.Co * e.Ci * gx_pack_src_elems(e.pack.view));
+    if (threadIdx.x == 0) *reinterpret_cast<float*>(reinterpret_cast<char*>(e.wp) + gx_pack_trailer_off(e.pack, e.Kpad, e.Mpad)) = r;
 }
 
 __global__ void pack_weights_batch_kernel(const PackEntry* __restrict__ entries, const int* __restrict__ map) {
     const PackEntry e = entries[map[blockIdx.x]];
-    const int total = e.NT * e.Kpad * e.Mpad;
+    const int total = gx_pack_taps(e.pack.view) * e.Kpad * e.Mpad;
     const int begin = (blockIdx.x - e.chunk0) * kPackChunk, end = begin + kPackChunk < total ? begin + kPackChunk : total;
-    // (45 / 46: the Winograd operands U = G g G^T, |U| <= 2.25 max |g|)
-    const int f16_exp = gx_pack_f16(e.pack) ? gx_f16_scale_exp(((e.pack == 45 || e.pack == 46) ? 2.25f : 1.f) * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(e.wp) + gx_kq_h_amax_off(e.Kpad, e.Mpad, e.NT))) : 0;
-    for (int idx = begin + threadIdx.x; idx < end; idx += blockDim.x) {
-        const int m = idx % e.Mpad;
-        const int k = (idx / e.Mpad) % e.Kpad;
-        const int t = idx / (e.Mpad * e.Kpad);
-        if (e.pack >= 70) { pack_b1_store(e.w, e.wp, e.pack, e.Co, e.Ci, m, k, t, e.Kpad, e.Mpad); continue; }
-        if (e.pack >= 20) { pack_h_store(e.w, e.wp, e.pack, e.Co, e.Ci, m, k, t, e.NT, e.Kpad, f16_exp); continue; }
-        e.wp[pack_dest(e.pack, idx, m, k, t, e.Kpad, e.NT)] = pack_weight_value(e.w, e.pack, e.Co, e.Ci, m, k, t);
-    }
+    pack_elements(e.w, e.wp, e.pack, e.Co, e.Ci, e.Kpad, e.Mpad, begin + threadIdx.x, end, blockDim.x);
 }
 
-// Packs w into `wp` (caller workspace) -- or, inside a refreshed cache window, returns the cached packing.
-int launch_pack(const float* w, float* wp, int pack, int Co, int Ci, int NT, int Kpad, int Mpad, hipStream_t s,
-                const float** wp_used) {
-    *wp_used = wp;
+// Packs w into `wp` (caller workspace) -- or, inside a refreshed cache window, returns the cached packing -- and says where the
+// packing's trailer is (null: the form has none).
+struct GxPacked { const float* wp; const float* w_amax; };
+int launch_pack(const float* w, float* wp, GxPack pack, int Co, int Ci, int Kpad, int Mpad, hipStream_t s, GxPacked* out) {
+    GX_CHECK_ARG(gx_pack_valid(pack), "launch_pack: no packing of view %d in form %d", (int)pack.view, (int)pack.form);
+    const float* used = wp;
+    bool cached = false;
     if (g_cache_active >= 0) {
         for (const PackEntry& e : g_caches[g_cache_active].entries)
-            if (e.w == w && e.pack == pack && e.Co == Co && e.Ci == Ci) { *wp_used = e.wp; return GX_OK; }
+            if (e.is(w, pack, Co, Ci)) { used = e.wp; cached = true; break; }
     }
+    out->wp = used;
+    out->w_amax = gx_pack_has_trailer(pack.form)
+                      ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(used) + gx_pack_trailer_off(pack, Kpad, Mpad))
+                      : nullptr;
+    if (cached) return GX_OK;
     if (g_cache_recording >= 0) {
         PackCache& c = g_caches[g_cache_recording];
         bool found = false;
-        for (const PackEntry& e : c.entries) found = found || (e.w == w && e.pack == pack && e.Co == Co && e.Ci == Ci);
+        for (const PackEntry& e : c.entries) found = found || e.is(w, pack, Co, Ci);
         if (!found) {
-            PackEntry e{w, nullptr, pack, Co, Ci, NT, Kpad, Mpad, 0};
-            const size_t pbytes = pack >= 70 ? (size_t)NT * Kpad * Mpad * 2
-                                              : (pack >= 20 ? gx_kq_deconv_h_pack_bytes(Kpad, Mpad, NT) : (size_t)NT * Kpad * Mpad * sizeof(float));
-            if (hipMalloc((void**)&e.wp, pbytes) != hipSuccess) {
+            PackEntry e{w, nullptr, pack, Co, Ci, Kpad, Mpad, 0};
+            if (hipMalloc((void**)&e.wp, gx_pack_bytes(pack, Kpad, Mpad)) != hipSuccess) {
                 gx_set_error("weight cache: hipMalloc failed");
                 return GX_ELAUNCH;
             }
             c.entries.push_back(e);
         }
     }
-    const int total = NT * Kpad * Mpad;
+    const int total = gx_pack_taps(pack.view) * Kpad * Mpad;
     const int blocks = gx_ceil_div(total, 256) > 1024 ? 1024 : gx_ceil_div(total, 256);
-    if (gx_pack_f16(pack)) {
-        const int rc = gx_kq_weight_amax_launch(w, Co * Ci * ((pack <= 41 || pack == 45 || pack == 46) ? 9 : 25), reinterpret_cast<float*>(reinterpret_cast<char*>(wp) + gx_kq_h_amax_off(Kpad, Mpad, NT)), s);
+    if (out->w_amax) {
+        const int rc = gx_kq_weight_amax_launch(w, Co * Ci * gx_pack_src_elems(pack.view), const_cast<float*>(out->w_amax), s);
         if (rc) return rc;
     }
     {
         GxProf pf(KID_PACK_WEIGHTS, s, 0.0, 8.0 * total);
-        hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, s, w, wp, pack, Co, Ci, NT, Kpad, Mpad);
+        hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, s, w, wp, pack, Co, Ci, Kpad, Mpad);
     }
     GX_CHECK_LAUNCH("pack_weights");
     return GX_OK;
+}
+
+// the form each family packs in now
+static GxPackForm kq_pack_form() { return gx_kq_f16_on() ? GX_FORM_F16X2 : (gx_kq_b1_on() ? GX_FORM_BF16X1 : GX_FORM_BF16X3); }
+// (F16X2: the input's maxima were handed in for the next launch, gx_conv_input_amax)
+static GxPackForm wino_pack_form() {
+    if (!gx_wino_h_on()) return GX_FORM_TAP_F32;
+    return gx_wino_f16_pending() ? GX_FORM_F16X2 : (gx_wino_b1_on() ? GX_FORM_BF16X1 : GX_FORM_BF16X3);
+}
+// the Winograd operand of the conv3x3 (view) with K reduction channels, in that form: chunks of 16 channels on the 16-bit pipe
+static int launch_wino_pack(const float* w, float* wp, GxPackView view, int Cout, int Cin, int K, int Mpad, hipStream_t s, GxPacked* out) {
+    const GxPackForm f = wino_pack_form();
+    return launch_pack(w, wp, {view, f}, Cout, Cin, gx_round_up(K, gx_pack_pipe16(f) ? 16 : 8), Mpad, s, out);
 }
 
 // conv3x3 plan: 256-pixel tiles; grids that would have to split the channel reduction use 128-pixel tiles instead
@@ -1818,6 +1743,12 @@ int plan_b1(TapPlan* pl, int ymult, const char* name) {
     p.g.act = g.act;
     *pl = p;
     return GX_OK;
+}
+// the form the tap-conv kernels' weights are packed in: one bf16 piece where the mode asks for it and the layer has such a plan
+// (then *pl is that plan)
+template <int MODE>
+GxPackForm tap_pack_form(TapPlan* pl, int ymult, const char* name) {
+    return gx_tapconv_b1_on() && plan_b1<MODE>(pl, ymult, name) == GX_OK ? GX_FORM_TAP_BF16X1 : GX_FORM_TAP_F32;
 }
 
 struct WgradPlan {
@@ -2398,7 +2329,7 @@ static size_t conv3x3_pack_floats(int Cin, int Cout) {
     // (24: the bf16-pipe Winograd operands are three 2-byte pieces per value on 16-channel chunks)
     size_t f = (size_t)24 * gx_round_up(Cin, 16) * gx_round_up(Cout, 64);
     size_t d = (size_t)24 * gx_round_up(Cout, 16) * gx_round_up(Cin, 64);
-    return (f > d ? f : d) + 4096;      // (+ the slack of the bf16-piece packings, kinds 20 / 21)
+    return (f > d ? f : d) + 4096;      // (+ the slack of the 16-bit-pipe packings)
 }
 
 int gx_weight_cache_create(void) {
@@ -2429,7 +2360,7 @@ int gx_weight_cache_record(int id, int on) {
         for (size_t i = 0; i < c.entries.size(); ++i) {
             PackEntry& e = c.entries[i];
             e.chunk0 = (int)map.size();
-            const int n = gx_ceil_div(e.NT * e.Kpad * e.Mpad, kPackChunk);
+            const int n = gx_ceil_div(e.total(), kPackChunk);
             map.insert(map.end(), (size_t)n, (int)i);
         }
         c.nchunks = (int)map.size();
@@ -2457,14 +2388,14 @@ int gx_weight_cache_refresh(int id, gx_stream_t stream) {
     if (c.entries.empty()) { g_cache_active = -1; return GX_OK; }
     hipStream_t s = (hipStream_t)stream;
     bool any_f16 = false;
-    for (const PackEntry& e : c.entries) any_f16 = any_f16 || gx_pack_f16(e.pack);
+    for (const PackEntry& e : c.entries) any_f16 = any_f16 || gx_pack_has_trailer(e.pack.form);
     if (any_f16) {
         GxProf pf(KID_SMALL_REDUCE, s, 0.0, 0.0);
         hipLaunchKernelGGL(pack_amax_batch_kernel, dim3((unsigned)c.entries.size()), dim3(1024), 0, s, (const PackEntry*)c.dev);
     }
     {
         double bytes = 0.0;
-        for (const PackEntry& e : c.entries) bytes += 8.0 * e.NT * e.Kpad * e.Mpad;
+        for (const PackEntry& e : c.entries) bytes += 8.0 * e.total();
         GxProf pf(KID_PACK_WEIGHTS, s, 0.0, bytes);
         hipLaunchKernelGGL(pack_weights_batch_kernel, dim3((unsigned)c.nchunks), dim3(256), 0, s,
                            (const PackEntry*)c.dev, (const int*)c.dev_map);
@@ -2561,45 +2492,40 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
     float* wp = (float*)ws;
     float* part = wp + conv3x3_pack_floats(Cin, Cout);
     pl.g.act = act;
-    const float* wpu;
+    GxPacked pk;
     const bool wino_ok = !bias && act == 0 && gx_wino_eligible(N, Cin, Cout, H, W);
     // <= 32 output channels: the bf16-pipe kernel with 32-channel workgroups, ahead of Winograd (whose 64-channel tile would be
     // half empty: MONet's UNet 64 -> 32 layer 51 -> 38 us)
     if (gx_kq_c3h_eligible(N, Cin, Cout, H, W)) {
-        const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 40: two fp16 pieces of w * 2^e (gx_kq_precision(2))
-        const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 60: one bf16 piece (gx_kq_precision(3))
-        rc = launch_pack(w, wp, 20 + f16 + b1, Cout, Cin, 9, gx_round_up(Cin, 16), Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {GX_VIEW_C3_FWD, kq_pack_form()}, Cout, Cin, gx_round_up(Cin, 16), Mpad, s, &pk);
         if (rc) return rc;
+        const bool f16 = pk.w_amax != nullptr;          // two fp16 pieces of w * 2^e (gx_kq_precision(2))
         float* amax_ws = f16 ? (float*)((char*)ws + gx_conv3x3_ws_bytes(N, Cin, Cout, H, W)) - gx_kq_amax_ws_floats() : nullptr;
         if (f16) { int unused_n; (void)gx_amax_link_take(nullptr, 0, &unused_n); }       // (a pending amax link is not for this call)
-        rc = gx_kq_c3h_launch(x, wpu, bias, act, y, N, Cin, Cout, H, W, s, nullptr, 0, amax_ws,
-                              f16 ? (const float*)((const char*)wpu + gx_kq_h_amax_off(gx_round_up(Cin, 16), Mpad, 9)) : nullptr);
+        rc = gx_kq_c3h_launch(x, pk.wp, bias, act, y, N, Cin, Cout, H, W, s, nullptr, 0, amax_ws, pk.w_amax);
         if (rc) return rc;
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
     if (!wino_ok && gx_kq_c3_eligible(N, Cin, Cout, H, W)) {   // 16-byte operand reads (gx_kq.hip)
-        rc = launch_pack(w, wp, 10, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {GX_VIEW_C3_FWD, GX_FORM_KQ_F32}, Cout, Cin, Kpad, Mpad, s, &pk);
         if (rc) return rc;
-        rc = gx_kq_c3_launch(x, wpu, bias, act, y, N, Cin, Cout, H, W, s);
+        rc = gx_kq_c3_launch(x, pk.wp, bias, act, y, N, Cin, Cout, H, W, s);
         if (rc) return rc;
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
     if (wino_ok) {   // Winograd F(2x2,3x3): 2.25x fewer MFMA passes
-        // (25: three bf16 pieces; 45: two fp16 pieces -- the input's maxima were handed in, gx_conv_input_amax)
-        rc = gx_wino_h_on() ? launch_pack(w, wp, gx_wino_f16_pending() ? 45 : (gx_wino_b1_on() ? 65 : 25), Cout, Cin, 16, gx_round_up(Cin, 16), Mpad, s, &wpu)
-                            : launch_pack(w, wp, 5, Cout, Cin, 16, Kpad, Mpad, s, &wpu);
+        rc = launch_wino_pack(w, wp, GX_VIEW_WINO_FWD, Cout, Cin, Cin, Mpad, s, &pk);
         if (rc) return rc;
-        rc = gx_wino_launch(x, wpu, y, N, Cin, Cout, H, W, s);
+        rc = gx_wino_launch(x, pk.wp, y, N, Cin, Cout, H, W, s);
         if (rc) return rc;
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
-    const bool b1 = gx_tapconv_b1_on() && plan_b1<M_C3>(&pl, 1, "gx_conv3x3_fwd") == GX_OK;
-    rc = launch_pack(w, wp, b1 ? 70 : 0, Cout, Cin, 9, Kpad, Mpad, s, &wpu);       // (70: one bf16 piece)
+    rc = launch_pack(w, wp, {GX_VIEW_C3_FWD, tap_pack_form<M_C3>(&pl, 1, "gx_conv3x3_fwd")}, Cout, Cin, Kpad, Mpad, s, &pk);
     if (rc) return rc;
-    rc = launch_tapconv<M_C3>(x, wpu, bias, pl.g.nsplit > 1 ? part : y, pl, s, "gx_conv3x3_fwd");
+    rc = launch_tapconv<M_C3>(x, pk.wp, bias, pl.g.nsplit > 1 ? part : y, pl, s, "gx_conv3x3_fwd");
     if (rc) return rc;
     if (parts_out) {          // the consumer (gx_gn_relu_fwd_parts) sums the split-K slabs itself
         *parts_out = pl.g.nsplit > 1 ? part : y;
@@ -2641,33 +2567,29 @@ static int conv3x3_dgrad_impl(const float* dy, const float* w, float* dx, int N,
     if (rc) return rc;
     float* wp = (float*)ws;
     float* part = wp + conv3x3_pack_floats(Cin, Cout);
-    const float* wpu;
+    GxPacked pk;
     const bool wino_ok = gx_wino_eligible(N, Cout, Cin, H, W);
     if (gx_kq_c3h_eligible(N, Cout, Cin, H, W)) {
-        const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 41
-        const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 61
-        rc = launch_pack(w, wp, 21 + f16 + b1, Cout, Cin, 9, gx_round_up(Cout, 16), Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {GX_VIEW_C3_DGRAD, kq_pack_form()}, Cout, Cin, gx_round_up(Cout, 16), Mpad, s, &pk);
         if (rc) return rc;
+        const bool f16 = pk.w_amax != nullptr;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_conv3x3_ws_bytes(N, Cin, Cout, H, W)) - gx_kq_amax_ws_floats() : nullptr;
         if (f16) { int unused_n; (void)gx_amax_link_take(nullptr, 0, &unused_n); }       // (a pending amax link is not for this call)
-        return gx_kq_c3h_launch(dy, wpu, nullptr, 0, dx, N, Cout, Cin, H, W, s, nullptr, 0, amax_ws,
-                                f16 ? (const float*)((const char*)wpu + gx_kq_h_amax_off(gx_round_up(Cout, 16), Mpad, 9)) : nullptr);
+        return gx_kq_c3h_launch(dy, pk.wp, nullptr, 0, dx, N, Cout, Cin, H, W, s, nullptr, 0, amax_ws, pk.w_amax);
     }
     if (!wino_ok && gx_kq_c3_eligible(N, Cout, Cin, H, W)) {
-        rc = launch_pack(w, wp, 11, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {GX_VIEW_C3_DGRAD, GX_FORM_KQ_F32}, Cout, Cin, Kpad, Mpad, s, &pk);
         if (rc) return rc;
-        return gx_kq_c3_launch(dy, wpu, nullptr, 0, dx, N, Cout, Cin, H, W, s);
+        return gx_kq_c3_launch(dy, pk.wp, nullptr, 0, dx, N, Cout, Cin, H, W, s);
     }
     if (wino_ok) {
-        rc = gx_wino_h_on() ? launch_pack(w, wp, gx_wino_f16_pending() ? 46 : (gx_wino_b1_on() ? 66 : 26), Cout, Cin, 16, gx_round_up(Cout, 16), Mpad, s, &wpu)
-                            : launch_pack(w, wp, 6, Cout, Cin, 16, Kpad, Mpad, s, &wpu);
+        rc = launch_wino_pack(w, wp, GX_VIEW_WINO_DGRAD, Cout, Cin, Cout, Mpad, s, &pk);
         if (rc) return rc;
-        return gx_wino_launch(dy, wpu, dx, N, Cout, Cin, H, W, s);
+        return gx_wino_launch(dy, pk.wp, dx, N, Cout, Cin, H, W, s);
     }
-    const bool b1 = gx_tapconv_b1_on() && plan_b1<M_C3>(&pl, 1, "gx_conv3x3_dgrad") == GX_OK;
-    rc = launch_pack(w, wp, b1 ? 71 : 1, Cout, Cin, 9, Kpad, Mpad, s, &wpu);
+    rc = launch_pack(w, wp, {GX_VIEW_C3_DGRAD, tap_pack_form<M_C3>(&pl, 1, "gx_conv3x3_dgrad")}, Cout, Cin, Kpad, Mpad, s, &pk);
     if (rc) return rc;
-    rc = launch_tapconv<M_C3>(dy, wpu, nullptr, pl.g.nsplit > 1 ? part : dx, pl, s, "gx_conv3x3_dgrad");
+    rc = launch_tapconv<M_C3>(dy, pk.wp, nullptr, pl.g.nsplit > 1 ? part : dx, pl, s, "gx_conv3x3_dgrad");
     if (rc) return rc;
     if (parts_out && pl.g.nsplit > 1) {       // the consumer sums the split-K slabs itself
         *parts_out = part; *nsplit_out = pl.g.nsplit;
@@ -2696,15 +2618,13 @@ int gx_conv3x3_dgrad_act(const float* dy, const float* w, const float* xout, int
     GX_CHECK_ARG(ws_bytes >= gx_conv3x3_dgrad_act_ws_bytes(N, Cin, Cout, H, W), "gx_conv3x3_dgrad_act: workspace too small");
     GX_CHECK_ARG(gx_conv3x3_dgrad_act_supported(N, Cin, Cout, H, W), "gx_conv3x3_dgrad_act: shape not supported (gx_conv3x3_dgrad_act_supported)");
     hipStream_t s = (hipStream_t)stream;
-    const float* wpu;
-    const int f16 = gx_kq_f16_on() ? 20 : 0;           // pack 41
-    const int b1 = gx_kq_b1_on() ? 40 : 0;             // pack 61
-    rc = launch_pack(w, (float*)ws, 21 + f16 + b1, Cout, Cin, 9, gx_round_up(Cout, 16), gx_round_up(Cin, 64), s, &wpu);
+    GxPacked pk;
+    rc = launch_pack(w, (float*)ws, {GX_VIEW_C3_DGRAD, kq_pack_form()}, Cout, Cin, gx_round_up(Cout, 16), gx_round_up(Cin, 64), s, &pk);
     if (rc) return rc;
+    const bool f16 = pk.w_amax != nullptr;
     float* amax_ws = f16 ? (float*)((char*)ws + gx_conv3x3_ws_bytes(N, Cin, Cout, H, W)) - gx_kq_amax_ws_floats() : nullptr;
     if (f16) { int unused_n; (void)gx_amax_link_take(nullptr, 0, &unused_n); }       // (a pending amax link is not for this call)
-    rc = gx_kq_c3h_launch(dy, wpu, nullptr, 0, dxa, N, Cout, Cin, H, W, s, xout, act, amax_ws,
-                          f16 ? (const float*)((const char*)wpu + gx_kq_h_amax_off(gx_round_up(Cout, 16), gx_round_up(Cin, 64), 9)) : nullptr);
+    rc = gx_kq_c3h_launch(dy, pk.wp, nullptr, 0, dxa, N, Cout, Cin, H, W, s, xout, act, amax_ws, pk.w_amax);
     if (rc || !dbias) return rc;
     float* part = (float*)((char*)ws + gx_round_up((long)gx_conv3x3_ws_bytes(N, Cin, Cout, H, W), 256));
     return gx_chan_sums_launch(dxa, N, Cin, H * W, part, dbias, s);
@@ -2872,7 +2792,7 @@ size_t gx_conv5x5s1_ws_bytes(int N, int K, int M, int H, int W) {
     if (plan_tapconv<M_C5>(N, K, M, gx_round_up(M, 64), H, W, H, W, H, W, 0, &pl, "ws") == GX_OK && pl.g.nsplit > 1)
         part = pl.g.nsplit * pl.out_elems;
     size_t b = ((size_t)25 * gx_round_up(K, 8) * gx_round_up(M, 64) + part) * sizeof(float);
-    const size_t bh = gx_kq_deconv_h_pack_bytes(gx_round_up(K, 16), gx_round_up(M, 64), 25);     // the bf16-pipe packing (kinds 27 / 28)
+    const size_t bh = gx_pack_bytes({GX_VIEW_C5, GX_FORM_BF16X3}, gx_round_up(K, 16), gx_round_up(M, 64));     // the 16-bit-pipe packing
     return (b > bh ? b : bh) + gx_kq_amax_ws_floats() * sizeof(float);       // (+ the fp16 x 3 form's amax scratch, at the end)
 }
 
@@ -2894,25 +2814,22 @@ int gx_conv5x5s1(const float* in, const float* w, float* out, int N, int K, int 
     if (rc) return rc;
     float* wp = (float*)ws;
     float* part = wp + (size_t)25 * Kpad * Mpad;
-    const float* wpu;
+    GxPacked pk;
+    // GX_VIEW_C5: w [M][K]; GX_VIEW_C5_FLIP: w [K][M] flipped (launch_pack's (Co, Ci) are the weight tensor's leading dimensions)
+    const GxPackView view = flip ? GX_VIEW_C5_FLIP : GX_VIEW_C5;
+    const int Co = flip ? K : M, Ci = flip ? M : K;
     if (gx_kq_c5h_eligible(N, K, M, H, W)) {       // chip-filling layers: on the bf16 matrix pipe (gx_kq.hip Q_C5H)
-        const int f16 = gx_kq_f16_on() ? 20 : 0;       // packs 47 / 48
-        const int b1 = gx_kq_b1_on() ? 40 : 0;         // packs 67 / 68
-        rc = flip ? launch_pack(w, wp, 28 + f16 + b1, K, M, 25, gx_round_up(K, 16), Mpad, s, &wpu)
-                  : launch_pack(w, wp, 27 + f16 + b1, M, K, 25, gx_round_up(K, 16), Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {view, kq_pack_form()}, Co, Ci, gx_round_up(K, 16), Mpad, s, &pk);
         if (rc) return rc;
+        const bool f16 = pk.w_amax != nullptr;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_conv5x5s1_ws_bytes(N, K, M, H, W)) - gx_kq_amax_ws_floats() : nullptr;
         int xn = 0;
         const float* xparts = f16 ? gx_amax_link_take(in, (size_t)N * K * H * W, &xn) : nullptr;      // the input's partial maxima from the kernel that wrote it (the gated unit)
-        return gx_kq_c5h_launch(in, wpu, out, N, K, M, H, W, s, amax_ws,
-                                f16 ? (const float*)((const char*)wpu + gx_kq_h_amax_off(gx_round_up(K, 16), Mpad, 25)) : nullptr,
-                                xparts, xn);
+        return gx_kq_c5h_launch(in, pk.wp, out, N, K, M, H, W, s, amax_ws, pk.w_amax, xparts, xn);
     }
-    // pack 7: w [M][K]; pack 8: w [K][M] flipped (launch_pack's (Co, Ci) are the weight tensor's leading dimensions)
-    const int b1 = gx_tapconv_b1_on() && plan_b1<M_C5>(&pl, 1, "gx_conv5x5s1") == GX_OK ? 70 : 0;     // packs 77 / 78: one bf16 piece
-    rc = flip ? launch_pack(w, wp, 8 + b1, K, M, 25, Kpad, Mpad, s, &wpu) : launch_pack(w, wp, 7 + b1, M, K, 25, Kpad, Mpad, s, &wpu);
+    rc = launch_pack(w, wp, {view, tap_pack_form<M_C5>(&pl, 1, "gx_conv5x5s1")}, Co, Ci, Kpad, Mpad, s, &pk);
     if (rc) return rc;
-    rc = launch_tapconv<M_C5>(in, wpu, nullptr, pl.g.nsplit > 1 ? part : out, pl, s, "gx_conv5x5s1");
+    rc = launch_tapconv<M_C5>(in, pk.wp, nullptr, pl.g.nsplit > 1 ? part : out, pl, s, "gx_conv5x5s1");
     if (rc) return rc;
     if (pl.g.nsplit > 1) return launch_splitk_reduce(part, nullptr, out, pl, s);
     return GX_OK;
@@ -2961,10 +2878,11 @@ static size_t deconv_pack_floats(int Cin, int Cout) {
     // fwd: two row-parity packs (15 + 10 taps, k=Cin, m=Cout); dgrad: 25 taps (k=Cout, m=Cin)
     size_t f = (size_t)25 * gx_round_up(Cin, 8) * gx_round_up(Cout, 64);
     size_t d = (size_t)25 * gx_round_up(Cout, 8) * gx_round_up(Cin, 64);
-    // (bf16-pipe forward, packs 22 / 23: three bf16 pieces per weight = 1.5 x, + the slack of whole-phase copies)
-    const size_t h = (gx_kq_deconv_h_pack_bytes(gx_round_up(Cin, 16), Cout, 15) + gx_kq_deconv_h_pack_bytes(gx_round_up(Cin, 16), Cout, 10)) / 4;
+    // (bf16-pipe forward: three bf16 pieces per weight = 1.5 x, + the slack of whole-phase copies)
+    const size_t h = (gx_pack_bytes({GX_VIEW_DT_ROW0, GX_FORM_BF16X3}, gx_round_up(Cin, 16), Cout) +
+                      gx_pack_bytes({GX_VIEW_DT_ROW1, GX_FORM_BF16X3}, gx_round_up(Cin, 16), Cout)) / 4;
     f = f > h ? f : h;
-    const size_t dh = gx_kq_deconv_h_pack_bytes(gx_round_up(Cout, 16), Cin, 25) / 4;
+    const size_t dh = gx_pack_bytes({GX_VIEW_DT_DGRAD, GX_FORM_BF16X3}, gx_round_up(Cout, 16), Cin) / 4;
     d = d > dh ? d : dh;
     return f > d ? f : d;
 }
@@ -3046,32 +2964,31 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
     float* wp0 = (float*)ws;
     float* wp1 = wp0 + (size_t)15 * Kpad * Mpad;
     float* part = wp0 + deconv_pack_floats(Cin, Cout);
-    const float *wpu0, *wpu1;
+    GxPacked pk0, pk1;
     if (stats_parts_out) *stats_parts_out = 0;
     if (gx_kq_deconv_h_eligible(N, Cin, Cout, Hin, Win)) {     // ... on the bf16 matrix pipe (fp32 products from bf16 pieces)
-        float* wh1 = wp0 + gx_kq_deconv_h_pack_bytes(Cin, Cout, 15) / 4;
-        const int f16 = gx_kq_f16_on() ? 20 : 0;       // packs 42 / 43: two fp16 pieces of w * 2^e (gx_kq_precision(2))
-        const int b1 = gx_kq_b1_on() ? 40 : 0;         // packs 62 / 63: one bf16 piece (gx_kq_precision(3))
-        rc = launch_pack(w, wp0, 22 + f16 + b1, Cout, Cin, 15, Cin, Mpad, s, &wpu0);
+        float* wh1 = wp0 + gx_pack_bytes({GX_VIEW_DT_ROW0, GX_FORM_BF16X3}, Cin, Cout) / 4;
+        const GxPackForm form = kq_pack_form();
+        rc = launch_pack(w, wp0, {GX_VIEW_DT_ROW0, form}, Cout, Cin, Cin, Mpad, s, &pk0);
         if (rc) return rc;
-        rc = launch_pack(w, wh1, 23 + f16 + b1, Cout, Cin, 10, Cin, Mpad, s, &wpu1);
+        rc = launch_pack(w, wh1, {GX_VIEW_DT_ROW1, form}, Cout, Cin, Cin, Mpad, s, &pk1);
         if (rc) return rc;
+        const bool f16 = pk0.w_amax != nullptr;         // two fp16 pieces of w * 2^e (gx_kq_precision(2))
         float* amax_ws = f16 ? (float*)((char*)ws + gx_deconv5x5s2_ws_bytes(N, Cin, Cout, Hin, Win)) - gx_kq_amax_ws_floats() : nullptr;
         int xn = 0;
         const float* xparts = f16 ? gx_amax_link_take(x, (size_t)N * Cin * Hin * Win, &xn) : nullptr;      // x's partial maxima from the kernel that wrote it
-        rc = gx_kq_deconv_fwd_h_launch(x, wpu0, wpu1, bias, y, N, Cin, Cout, Hin, Win, stats, stats_parts_out, s, amax_ws,
-                                       f16 ? (const float*)((const char*)wpu0 + gx_kq_h_amax_off(Cin, Mpad, 15)) : nullptr,
-                                       xparts, xn);
+        rc = gx_kq_deconv_fwd_h_launch(x, pk0.wp, pk1.wp, bias, y, N, Cin, Cout, Hin, Win, stats, stats_parts_out, s, amax_ws,
+                                       pk0.w_amax, xparts, xn);
         if (rc) return rc;
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
     }
     if (gx_kq_deconv_eligible(N, Cin, Cout, Hin, Win, 2)) {   // chip-filling layers: 16-byte operand reads (gx_kq.hip)
-        rc = launch_pack(w, wp0, 12, Cout, Cin, 15, Kpad, Mpad, s, &wpu0);
+        rc = launch_pack(w, wp0, {GX_VIEW_DT_ROW0, GX_FORM_KQ_F32}, Cout, Cin, Kpad, Mpad, s, &pk0);
         if (rc) return rc;
-        rc = launch_pack(w, wp1, 13, Cout, Cin, 10, Kpad, Mpad, s, &wpu1);
+        rc = launch_pack(w, wp1, {GX_VIEW_DT_ROW1, GX_FORM_KQ_F32}, Cout, Cin, Kpad, Mpad, s, &pk1);
         if (rc) return rc;
-        rc = gx_kq_deconv_fwd_launch(x, wpu0, wpu1, bias, y, N, Cin, Cout, Hin, Win, stats, stats_parts_out, s);
+        rc = gx_kq_deconv_fwd_launch(x, pk0.wp, pk1.wp, bias, y, N, Cin, Cout, Hin, Win, stats, stats_parts_out, s);
         if (rc) return rc;
         if (parts_out) { *parts_out = y; *nsplit_out = 1; }
         return GX_OK;
@@ -3087,11 +3004,13 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
                                 2, 128) == GX_OK)
             p0 = p2;
     }
-    const int b1 = gx_tapconv_b1_on() && plan_b1<M_DT0>(&p0, 2, "gx_deconv5x5s2_fwd") == GX_OK ? 70 : 0;    // packs 72 / 73
-    rc = launch_pack(w, wp0, 2 + b1, Cout, Cin, 15, Kpad, Mpad, s, &wpu0);
+    const GxPackForm form = tap_pack_form<M_DT0>(&p0, 2, "gx_deconv5x5s2_fwd");
+    const bool b1 = form == GX_FORM_TAP_BF16X1;
+    rc = launch_pack(w, wp0, {GX_VIEW_DT_ROW0, form}, Cout, Cin, Kpad, Mpad, s, &pk0);
     if (rc) return rc;
-    rc = launch_pack(w, wp1, 3 + b1, Cout, Cin, 10, Kpad, Mpad, s, &wpu1);
+    rc = launch_pack(w, wp1, {GX_VIEW_DT_ROW1, form}, Cout, Cin, Kpad, Mpad, s, &pk1);
     if (rc) return rc;
+    const float *wpu0 = pk0.wp, *wpu1 = pk1.wp;
     float* dst = p0.g.nsplit > 1 ? part : y;
     if (stats_parts_out) *stats_parts_out = 0;
     {
@@ -3158,23 +3077,20 @@ int gx_deconv5x5s2_dgrad(const float* dy, const float* w, float* dx, int N, int 
     hipStream_t s = (hipStream_t)stream;
     float* wp = (float*)ws;
     float* part = wp + deconv_pack_floats(Cin, Cout);
-    const float* wpu;
+    GxPacked pk;
     if (gx_kq_deconv_dgrad_h_eligible(N, Cout, Cin_out, Hin, Win)) {     // on the bf16 matrix pipe
-        const int f16 = gx_kq_f16_on() ? 20 : 0;       // pack 44 (gx_kq_precision(2))
-        const int b1 = gx_kq_b1_on() ? 40 : 0;         // pack 64 (gx_kq_precision(3))
-        rc = launch_pack(w, wp, 24 + f16 + b1, Cout, Cin, 25, Cout, Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {GX_VIEW_DT_DGRAD, kq_pack_form()}, Cout, Cin, Cout, Mpad, s, &pk);
         if (rc) return rc;
+        const bool f16 = pk.w_amax != nullptr;
         float* amax_ws = f16 ? (float*)((char*)ws + gx_deconv5x5s2_ws_bytes(N, Cin, Cout, Hin, Win)) - gx_kq_amax_ws_floats() : nullptr;
         int xn = 0;
         const float* xparts = f16 ? gx_amax_link_take(dy, (size_t)N * Cout * 4 * Hin * Win, &xn) : nullptr;     // dy's partial maxima from the kernel that wrote it
-        return gx_kq_deconv_dgrad_h_launch(dy, wpu, dx, N, Cout, Cin_out, Hin, Win, s, amax_ws,
-                                           f16 ? (const float*)((const char*)wpu + gx_kq_h_amax_off(Cout, Mpad, 25)) : nullptr,
-                                           xparts, xn);
+        return gx_kq_deconv_dgrad_h_launch(dy, pk.wp, dx, N, Cout, Cin_out, Hin, Win, s, amax_ws, pk.w_amax, xparts, xn);
     }
     if (gx_kq_deconv_eligible(N, Cout, Cin_out, Hin, Win, 1)) {
-        rc = launch_pack(w, wp, 14, Cout, Cin, 25, Kpad, Mpad, s, &wpu);
+        rc = launch_pack(w, wp, {GX_VIEW_DT_DGRAD, GX_FORM_KQ_F32}, Cout, Cin, Kpad, Mpad, s, &pk);
         if (rc) return rc;
-        return gx_kq_deconv_dgrad_launch(dy, wpu, dx, N, Cout, Cin_out, Hin, Win, s);
+        return gx_kq_deconv_dgrad_launch(dy, pk.wp, dx, N, Cout, Cin_out, Hin, Win, s);
     }
     TapPlan pl;
     rc = plan_tapconv<M_DG>(N, Cout, Cin_out, Mpad, Hin, Win, 2 * Hin, 2 * Win, Hin, Win, 0, &pl, "gx_deconv5x5s2_dgrad");
@@ -3185,10 +3101,9 @@ int gx_deconv5x5s2_dgrad(const float* dy, const float* w, float* dx, int N, int 
                                "gx_deconv5x5s2_dgrad", 1, 128) == GX_OK)
             pl = p2;
     }
-    const bool b1 = gx_tapconv_b1_on() && plan_b1<M_DG>(&pl, 1, "gx_deconv5x5s2_dgrad") == GX_OK;
-    rc = launch_pack(w, wp, b1 ? 74 : 4, Cout, Cin, 25, Kpad, Mpad, s, &wpu);      // (74: one bf16 piece)
+    rc = launch_pack(w, wp, {GX_VIEW_DT_DGRAD, tap_pack_form<M_DG>(&pl, 1, "gx_deconv5x5s2_dgrad")}, Cout, Cin, Kpad, Mpad, s, &pk);
     if (rc) return rc;
-    rc = launch_tapconv<M_DG>(dy, wpu, nullptr, pl.g.nsplit > 1 ? part : dx, pl, s, "gx_deconv5x5s2_dgrad");
+    rc = launch_tapconv<M_DG>(dy, pk.wp, nullptr, pl.g.nsplit > 1 ? part : dx, pl, s, "gx_deconv5x5s2_dgrad");
     if (rc) return rc;
     if (pl.g.nsplit > 1) return launch_splitk_reduce(part, nullptr, dx, pl, s);
     return GX_OK;

@@ -53,7 +53,7 @@ template <> struct QCfg<Q_C3> {
     __host__ __device__ static constexpr int cls(int, int) { return 0; }
 };
 // ConvTranspose k5 s2 p2 op1, output rows 2r + a: kh = 2 p + a, halo row offset 2 - p; kw = i, halo column offset
-// 2 - i / 2, output column parity i & 1 (same tap order as gx_conv.hip's packs 2 / 3).
+// 2 - i / 2, output column parity i & 1 (same tap order as GX_VIEW_DT_ROW0 / _ROW1, gx_pack.h).
 template <> struct QCfg<Q_DT0> {
     static constexpr int NPH = 3, NT = 15, MAXT = 5, NCLS = 2;
     static constexpr bool PLANE_PER_PHASE = false;
@@ -89,7 +89,7 @@ template <> struct QCfg<Q_DG> {
 // piece products, v_mfma_f32_32x32x16_bf16 (k = 16 channels: lane half h supplies the 8 consecutive channels of octet h).
 // A chunk is 16 channels; the input tile is split into its three bf16 planes ONCE, by the staging
 //     input   [piece 3][octet 2][halo position][8 channels (bf16)]      single-buffered (the next chunk waits in registers)
-//     weights [tap][piece 3][octet 2][64 output channels][8 channels]   pre-split by the pack kernel (packs 22 / 23)
+//     weights [tap][piece 3][octet 2][64 output channels][8 channels]   pre-split by the pack kernel (GX_VIEW_DT_ROW0 / _ROW1 in GX_FORM_BF16X3)
 // so the tap loop has no VALU work: 12 ds_read_b128 per 24 MFMAs of 32 cycles.  Phases of <= 3 taps (a kernel row kh =
 // taps {0,1,2} | {3,4}) keep input + double-buffered weights at 72 KB: two workgroups per CU as before.
 template <int PA> struct QCfgDTH {
@@ -123,7 +123,7 @@ template <> struct QCfg<Q_DGH> {
 };
 // conv3x3 (forward / data gradient) of layers with <= 32 output channels there (the BroadcastDecoder's 32 -> 32 convs on the
 // (S + 2L)^2 canvas, modules/decoders.py:21-35): one phase per kernel row; a workgroup owns 32 output channels (MI = 1), so the
-// weight slices are half as large ([tap][piece 3][octet 2][32 output channels][8 channels], pack kinds 20 / 21) and input
+// weight slices are half as large ([tap][piece 3][octet 2][32 output channels][8 channels], GX_VIEW_C3_FWD / _DGRAD in the 16-bit-pipe forms) and input
 // + weights stay at 72 KB with the 4-slot halo tiles of grids that are not powers of two (8 x 8 pixels x 4 images)
 template <> struct QCfg<Q_C3H> {
     static constexpr int NPH = 3, NT = 9, MAXT = 3, NCLS = 1;
@@ -164,7 +164,7 @@ typedef _Float16 q_f16x8 __attribute__((ext_vector_type(8)));
 // plane and one-piece weight taps in LDS (a third of the bf16 form's), no scale: bf16 has fp32's exponent range.
 enum { PF_B6 = 0, PF_F3 = 1, PF_B1 = 2 };
 constexpr int QH_TAP_BYTES = 3 * 2 * 64 * 16;          // one tap of one 16-channel chunk: 6144 B
-static_assert(QH_TAP_BYTES == 6144, "gx_kq_h_amax_off (gx_common.h) spells this number out");
+static_assert(QH_TAP_BYTES == 6144, "gx_kq_h_amax_off (gx_pack.h) spells this number out");
 // output-channel rows of a workgroup's weight slice and the bytes of one (tap, chunk) of it
 // (NP pieces per value: three bf16 ones, two fp16 ones, one bf16 one)
 template <int MODE, int PF = PF_B6> struct QHLay {
@@ -1089,7 +1089,7 @@ int gx_kq_deconv_fwd_launch(const float* in, const float* wp0, const float* wp1,
     return GX_OK;
 }
 
-// ---- the transposed conv forward on the bf16 matrix pipe (packs 22 / 23: weights pre-split into bf16 pieces)
+// ---- the transposed conv forward on the bf16 matrix pipe (GX_VIEW_DT_ROW0 / _ROW1: weights pre-split into bf16 pieces)
 static int g_kq_h = -1;     // 1 (default): eligible layers run there; GENESIS_KQ_BF16X6=0 / gx_kq_precision(0): fp32 pipe
 static void kq_h_init() {
     if (g_kq_h >= 0) return;
@@ -1201,9 +1201,6 @@ static int kq_fold_parts(const float** parts, int* n, float* amax_ws, hipStream_
     *parts = amax_ws; *n = 1;
     return GX_OK;
 }
-size_t gx_kq_deconv_h_pack_bytes(int K, int M, int nt) {     // one row parity's packed weights (+ slack: whole-phase copies)
-    return (size_t)gx_ceil_div(M, 64) * (K / 16) * nt * QH_TAP_BYTES + 16384;
-}
 // LDS of the bf16-pipe transposed-conv kernels: three input piece planes (exact at four staging rounds) + two weight buffers;
 // 0: the tile does not leave room for two workgroups per CU
 // (np < 3: the launch's allocation in the fp16 x 3 form -- two planes, two-piece weight taps: 48 KB at three staging rounds, i.e. THREE
@@ -1228,7 +1225,7 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
     if (!q_plan(N, K, M, Hb, Wb, Hb, Wb, 2 * Hb, 2 * Wb, &g, &nq, &lds, 5) || qh_lds(g, nq) == 0 || K % 16 != 0) {
         gx_set_error("kq deconv fwd (bf16 pipe): shape not eligible"); return GX_EINVAL;
     }
-    const bool b1 = gx_kq_b1_on() && !amax_ws;          // one bf16 piece (packs 62 / 63)
+    const bool b1 = gx_kq_b1_on() && !amax_ws;          // one bf16 piece (GX_FORM_BF16X1)
     lds = qh_lds(g, nq, b1 ? 1 : (amax_ws ? 2 : 3));
     const bool st = stats && g.lG == 0 && (M % 8) == 0;
     if (stats_parts) *stats_parts = 0;
@@ -1269,7 +1266,7 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
     return GX_OK;
 }
 
-// ---- conv3x3 of <= 32-output-channel layers on the bf16 pipe (pack kinds 20 / 21); grids need not be powers of two: the
+// ---- conv3x3 of <= 32-output-channel layers on the bf16 pipe (GX_VIEW_C3_FWD / _DGRAD); grids need not be powers of two: the
 //      256-pixel tile takes the largest power-of-two divisors of the width and height, images fill the rest
 static bool q_plan_c3h(int N, int K, int M, int H, int W, QGeom* g, int* nq, size_t* lds_bytes) {
     if (K % 16 != 0 || H * W > 65536 || (double)N * K * H * W * 4.0 >= 2.0e9) return false;
@@ -1306,7 +1303,7 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
     const float* x_parts = nullptr; int x_nparts = 0;
     if (!q_plan_c3h(N, K, M, H, W, &g, &nq, &lds)) { gx_set_error("kq conv3x3 (bf16 pipe): shape not eligible"); return GX_EINVAL; }
     g.act = act; g.mask = mask; g.mask_act = mask_act;
-    const bool b1 = gx_kq_b1_on() && !amax_ws;           // one bf16 piece (packs 60 / 61)
+    const bool b1 = gx_kq_b1_on() && !amax_ws;           // one bf16 piece (GX_FORM_BF16X1)
     if (b1) {
         constexpr int NW1 = (3 * (QHLay<Q_C3H, PF_B1>::TAPB / 16) + 255) / 256;
         lds = (size_t)nq * 256 * 16 + (size_t)NW1 * 256 * 16;             // one input plane + one one-piece weight buffer
@@ -1332,7 +1329,7 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
         if (b1) {
             if (nq == 3) { q_set_attr(&kq_c3h_kernel<3, PF_B1>, &b3); hipLaunchKernelGGL((kq_c3h_kernel<3, PF_B1>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
             else { q_set_attr(&kq_c3h_kernel<4, PF_B1>, &b4); hipLaunchKernelGGL((kq_c3h_kernel<4, PF_B1>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
-        } else if (amax_ws) {          // fp16 x 3 (packs 40 / 41)
+        } else if (amax_ws) {          // fp16 x 3 (GX_FORM_F16X2)
             g.x_amax = x_parts ? x_parts : amax_ws; g.w_amax = w_amax;
             if (x_parts) g.x_amax_n = x_nparts;
             static bool t3 = false, t4 = false;
@@ -1351,7 +1348,7 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
     return GX_OK;
 }
 
-// ---- 5 x 5 stride-1 conv on the bf16 pipe (pack kinds 27 / 28)
+// ---- 5 x 5 stride-1 conv on the bf16 pipe (GX_VIEW_C5 / _C5_FLIP)
 static bool q_plan_c5h(int N, int K, int M, int H, int W, QGeom* g, size_t* lds_bytes) {
     if (K % 16 != 0 || H % 16 != 0 || W % 16 != 0 || H * W > 65536 || (double)N * K * H * W * 4.0 >= 2.0e9) return false;
     g->N = N; g->K = K; g->M = M; g->nchunks = K / 8;
@@ -1374,7 +1371,7 @@ int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K,
                      float* amax_ws, const float* w_amax, const float* x_parts, int x_nparts) {
     QGeom g; size_t lds;
     if (!q_plan_c5h(N, K, M, H, W, &g, &lds)) { gx_set_error("kq conv5x5 (bf16 pipe): shape not eligible"); return GX_EINVAL; }
-    const bool b1 = gx_kq_b1_on() && !amax_ws;           // one bf16 piece (packs 67 / 68)
+    const bool b1 = gx_kq_b1_on() && !amax_ws;           // one bf16 piece (GX_FORM_BF16X1)
     if (b1) {
         constexpr int NW1 = (3 * (QHLay<Q_C5H, PF_B1>::TAPB / 16) + 255) / 256;
         lds = (size_t)2 * (20 * 20) * 16 + (size_t)2 * NW1 * 256 * 16;
@@ -1393,7 +1390,7 @@ int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K,
         if (b1) {
             q_set_attr(&kq_c5h_kernel<4, PF_B1>, &b4);
             hipLaunchKernelGGL((kq_c5h_kernel<4, PF_B1>), grid, dim3(256), lds, s, in, wp, out, g);
-        } else if (amax_ws) {          // fp16 x 3 (packs 47 / 48)
+        } else if (amax_ws) {          // fp16 x 3 (GX_FORM_F16X2)
             g.x_amax = x_parts ? x_parts : amax_ws; g.w_amax = w_amax;
             if (x_parts) g.x_amax_n = x_nparts;
             q_set_attr(&kq_c5h_kernel<4, true>, &f4);
@@ -1418,7 +1415,7 @@ int gx_kq_deconv_dgrad_h_launch(const float* dy, const float* wp, float* dx, int
     if (!q_plan(N, K, M, Hb, Wb, 2 * Hb, 2 * Wb, Hb, Wb, &g, &nq, &lds, 9) || qh_lds(g, nq) == 0 || K % 16 != 0) {
         gx_set_error("kq deconv dgrad (bf16 pipe): shape not eligible"); return GX_EINVAL;
     }
-    const bool b1 = gx_kq_b1_on() && !amax_ws;          // one bf16 piece (pack 64)
+    const bool b1 = gx_kq_b1_on() && !amax_ws;          // one bf16 piece (GX_FORM_BF16X1)
     lds = qh_lds(g, nq, b1 ? 1 : (amax_ws ? 2 : 3));
     if (amax_ws && !x_parts) { const int rc = gx_kq_amax_launch(dy, (size_t)N * K * 4 * Hb * Wb, amax_ws, s); if (rc) return rc; }
     else if (amax_ws) { const int rc = kq_fold_parts(&x_parts, &x_nparts, amax_ws, s); if (rc) return rc; }

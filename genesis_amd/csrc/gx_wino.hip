@@ -50,7 +50,7 @@ struct WinoGeom {
     int xn0, xn1;
 };
 
-// U in the conv kernel's operand order (gx_common.h: gx_wino_u_value / gx_wino_u_slot)
+// U in the conv kernel's operand order (gx_pack.h: gx_wino_u_value / gx_wino_u_slot)
 __global__ void wino_pack_kernel(const float* __restrict__ w, float* __restrict__ U, int mode, int Co, int Ci, int Kpad,
                                  int Mpad) {
     const int total = 16 * Kpad * Mpad;
@@ -423,7 +423,7 @@ __device__ __forceinline__ void wino_split8_f16(const float (&v)[8], float sc, w
 //           loads).  Twice the tiles per A operand halve that traffic per MFMA, and the register budget pays for an A
 //           prefetch three positions deep instead of one.
 // PF: the piece form -- 0 three bf16 pieces (six piece products), 1 two fp16 pieces (three), 2 ONE bf16 piece (one product: U packed as
-// one bf16 plane, kinds 65 / 66; V rounded to bf16 in registers; both round to nearest even)
+// one bf16 plane, the Winograd views in GX_FORM_BF16X1; V rounded to bf16 in registers; both round to nearest even)
 enum { WPF_B6 = 0, WPF_F3 = 1, WPF_B1 = 2 };
 template <int NB, int PF = WPF_B6> struct WHCfg {
     static constexpr int TROWS = 4 * NB;                  // Winograd tile rows per workgroup (8 columns)
@@ -441,7 +441,7 @@ template <int NB, int PF = WPF_B6> struct WHCfg {
     static constexpr int POSB = (PF == WPF_B1 ? 1 : 3) * 2048;                // bytes of one position's A operands (fp16: slot 2 unused)
 };
 
-// F16: the operands as TWO fp16 pieces (U * 2^eU packed that way: kinds 45 / 46; V * 2^eV split in registers), three piece products
+// F16: the operands as TWO fp16 pieces (U * 2^eU packed that way: GX_FORM_F16X2; V * 2^eV split in registers), three piece products
 // per fp32 product instead of six -- half the MFMAs, two thirds of the A-operand traffic, a 24-VALU split per octet instead of 44.
 // eU from the weight tensor's largest magnitude (the packing's trailer; |U| <= 2.25 max |g|), eV from the INPUT tensor's, handed
 // over by the kernel that wrote it (g.xam*; |V| <= 4 max |d|); the outputs are scaled back by 2^-(eU + eV).
@@ -549,7 +549,7 @@ wino_conv_h_kernel(const float* __restrict__ in, const float* __restrict__ in2, 
         for (int of = 32; of >= 1; of >>= 1) xm = fmaxf(xm, __shfl_xor(xm, of, 64));
         const int eV = gx_f16_scale_exp(4.f * xm);
         const float wam = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(U) + gx_kq_h_amax_off(g.Kpad, g.Mpad, 16));
-        const int eU = gx_f16_scale_exp(2.25f * wam);
+        const int eU = gx_f16_scale_exp(2.25f * wam);      // (= gx_pack_amax_bound of the Winograd views: the pack scaled U by this)
         scV = ldexpf(1.f, eV);
         f16_back = -(eU + eV);
     }
@@ -728,7 +728,7 @@ __device__ __forceinline__ void wino_h_store(unsigned* __restrict__ U, float v0,
 __global__ void wino_pack_h_kernel(const float* __restrict__ w, unsigned* __restrict__ U, int mode, int Co, int Ci, int Kpad16,
                                    int Mpad, const float* __restrict__ amax, int b1) {
     const int total = 16 * (Kpad16 / 2) * Mpad;
-    const int f16_exp = amax ? gx_f16_scale_exp(2.25f * *amax) : 0;
+    const int f16_exp = amax ? gx_f16_scale_exp(gx_pack_amax_bound(GX_VIEW_WINO_FWD) * *amax) : 0;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int m = idx % Mpad, k = 2 * ((idx / Mpad) % (Kpad16 / 2)), p = idx / (Mpad * (Kpad16 / 2));
         wino_h_store(U, gx_wino_u_value(w, mode, Co, Ci, m, k, p), gx_wino_u_value(w, mode, Co, Ci, m, k + 1, p), m, k, p, Kpad16,
@@ -753,7 +753,7 @@ __global__ void wino_pack_pair_h_kernel(const float* __restrict__ w1, const floa
         float* tf = reinterpret_cast<float*>(reinterpret_cast<char*>(Uf) + gx_kq_h_amax_off(KpadF, MpadF, 16));
         float* td = reinterpret_cast<float*>(reinterpret_cast<char*>(Ud) + gx_kq_h_amax_off(KpadD, MpadD, 16));
         const float am = fmaxf(tf[1], tf[2]);          // (slots 1, 2: the two tensors' maxima; slot 0: their maximum, what the conv kernel reads)
-        f16_exp = gx_f16_scale_exp(2.25f * am);
+        f16_exp = gx_f16_scale_exp(gx_pack_amax_bound(GX_VIEW_WINO_FWD) * am);
         if (blockIdx.x == 0 && threadIdx.x == 0) { tf[0] = am; td[0] = am; }
     }
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < totF + totD; idx += gridDim.x * blockDim.x) {
@@ -809,7 +809,7 @@ static bool wino_f16_on() {
 }
 int gx_wino_mode_now(void) { return !gx_wino_h_on() ? 0 : (gx_wino_b1_on() ? 3 : (wino_f16_on() ? 2 : 1)); }
 namespace { struct WinoHint { const float* p0; const float* p1; int n0, n1; }; thread_local WinoHint t_wino_hint = {nullptr, nullptr, 0, 0}; }
-// true: the NEXT Winograd launch of this thread runs on fp16 pieces (the caller packs kinds 45 / 46 for it)
+// true: the NEXT Winograd launch of this thread runs on fp16 pieces (the caller packs GX_FORM_F16X2 for it)
 // (every workgroup of the Winograd kernel reduces the partial maxima itself: worth it up to ~1500 of them -- GroupNorm(8) at any batch
 //  of this workload has N x 8, the 128 x 128 model's pair data gradient 1280; InstanceNorm -- MONet's UNet, one partial per (image,
 //  channel) -- has up to 8192: measured 14.7 against 12.2 us per launch on its layers, so those stay on bf16 pieces)
@@ -851,9 +851,9 @@ bool gx_wino_eligible(int N, int K, int M, int H, int W) {
 // in2 / K1, out2 / M1: the pair variants (WinoGeom); nullptr / 0 for one input tensor and one output tensor
 static int wino_launch(const float* in, const float* in2, int K1, const float* U, float* out, float* out2, int M1, int N,
                        int K, int M, int H, int W, hipStream_t s) {
-    const bool h = gx_wino_h_on();          // (the operands in U were packed for the same pipe: wino_kpad / the pack kinds)
+    const bool h = gx_wino_h_on();          // (the operands in U were packed for the same pipe: wino_kpad / the pack forms)
     const bool f16 = gx_wino_f16_pending(); // (... and, with the input's maxima handed in, as fp16 pieces: the caller asked the same question)
-    const bool b1 = gx_wino_b1_on();        // (... or as one bf16 piece: packs 65 / 66)
+    const bool b1 = gx_wino_b1_on();        // (... or as one bf16 piece: GX_FORM_BF16X1)
     WinoGeom g;
     g.xam0 = f16 ? t_wino_hint.p0 : nullptr; g.xn0 = f16 ? t_wino_hint.n0 : 0;
     g.xam1 = f16 ? t_wino_hint.p1 : nullptr; g.xn1 = f16 ? t_wino_hint.n1 : 0;

@@ -143,8 +143,8 @@ int gx_matmul_precision_get(void);
  *      power of two), a switch of its own beside gx_matmul_precision:
  *        0  -- the default: the tap-conv kernels multiply on the fp32 pipe (v_mfma_f32_32x32x2_f32), the strips from six bf16 piece
  *              products (fp32 accuracy);
- *        3  -- medium: every operand rounded ONCE to bf16 (round to nearest even) -- the packed weights one bf16 plane (pack kinds
- *              70 ..), the input halo tile converted on its way into LDS, one v_mfma_f32_32x32x16_bf16 per k-step (two taps x 8
+ *        3  -- medium: every operand rounded ONCE to bf16 (round to nearest even) -- the packed weights one bf16 plane (the
+ *              tap-conv one-bf16 pack form), the input halo tile converted on its way into LDS, one v_mfma_f32_32x32x16_bf16 per k-step (two taps x 8
  *              channels), fp32 accumulation; the strips split every window row and dy value into one piece and issue one MFMA per
  *              tap.  About 2^-8 relative error per product, fp32's exponent range.  Split-K partials, their reduce launches and the
  *              strips' two fixed-order reduce launches are unchanged: results stay bit-reproducible.  The input is staged through

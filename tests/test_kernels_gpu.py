@@ -1521,7 +1521,7 @@ def test_conv3x3_to_32_channels_on_the_bf16_pipe(N, Cin, Cout, H, W):
     err = {}
     _lib.call('gx_kq_policy', 2)                  # every eligible shape (the default asks for a chip-filling grid)
     try:
-        for mode in (0, 1, 2):       # 2: three fp16 piece products (packs 40 / 41)
+        for mode in (0, 1, 2):       # 2: three fp16 piece products (GX_FORM_F16X2)
             _lib.call('gx_kq_precision', mode)
             y = hip.conv3x3_bias_act_fwd(x.to(DEV), w.to(DEV), b.to(DEV), 'elu')
             dx = hip.conv3x3_dgrad(dy.to(DEV), w.to(DEV))
