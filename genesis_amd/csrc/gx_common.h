@@ -290,6 +290,15 @@ bool gx_wstrip_supported(int N, int C, int H, int W);
 // the mode the last such launch of this thread ran in (gx_tapconv_last_mode)
 bool gx_tapconv_b1_on(void);
 void gx_tapconv_note(int mode);
+// gx_conv_last_plan (gx_conv.hip): the tile plan of this thread's last forward / data-gradient conv launch.  Every launcher fills
+// one of these from the values it launches with (never from the shape again) and notes it on the host just before the launch;
+// helper launches (packing, amax passes, reduces) note nothing.  The field order is the ABI's (GX_PLAN_* indices).
+struct GxConvPlan {
+    int family, form, lTH, lTW, lG, nq, pixels, rt_th, rt_tw, tiles_h, tiles_w, grid_x, grid_y, grid_z, nsplit, chunks_per_split,
+        nfull, stats;
+};
+static_assert(sizeof(GxConvPlan) == GX_PLAN_FIELDS * sizeof(int), "GxConvPlan and GX_PLAN_FIELDS disagree");
+void gx_conv_plan_note(const GxConvPlan& p);
 size_t gx_wstrip_ws_floats(int N, int C, int H, int W);
 int gx_wstrip_launch(const float* x, const float* dy, float* dw, float* dbias, int N, int C, int H, int W, void* ws, hipStream_t s);
 bool gx_wgq_bf16_pipe(void);      // gx_wgq_precision / GENESIS_WGQ_BF16X6: weight gradients on the bf16 matrix pipe (six piece products)

@@ -1495,7 +1495,12 @@ int plan_tapconv(int N, int K, int M, int Mpad_pack, int Hb, int Wb, int Hi, int
     const int need = gx_ceil_div(CHS, 256);
     const int lo = (MODE == M_DG) ? 8 : 2;
     pl->npos = need <= lo ? lo : 2 * lo;
-    if (need > 2 * lo) { gx_set_error("%s: halo tile too large (%d floats/channel)", name, CHS); return GX_EINVAL; }
+    if (need > 2 * lo) {
+        // (a 1 x 4 grid: no 256-pixel tile holds the halos of its 64 images -- 32 images per 128-pixel tile fit)
+        if (npix == 256) return plan_tapconv<MODE>(N, K, M, Mpad_pack, Hb, Wb, Hi, Wi, Ho, Wo, par_a, pl, name, ymult, 128, b1, max_split);
+        gx_set_error("%s: halo tile too large (%d floats/channel)", name, CHS);
+        return GX_EINVAL;
+    }
     pl->lds_bytes = b1 ? (size_t)2 * 16 * (CHS + TC::NT * 64) : (size_t)2 * (TC::KC * CHS + TC::NT * TC::KC * 64) * sizeof(float);
     if (pl->lds_bytes > 160 * 1024) { gx_set_error("%s: LDS %zu > 160KiB", name, pl->lds_bytes); return GX_EINVAL; }
     const int ptiles = g.tiles_h * g.tiles_w * gx_ceil_div(N, G);
@@ -1582,6 +1587,13 @@ void launch_dt(dim3 grid, size_t lds_bytes, hipStream_t s, const float* x, const
                        dst, g);
 }
 
+// the record of a tap-conv launch (gx_conv_last_plan): everything from the plan and the grid the launch uses
+void note_tap_plan(int family, const TapPlan& pl, dim3 grid, bool stats) {
+    const ConvGeom& g = pl.g;
+    gx_conv_plan_note({family, pl.b1 ? 3 : 0, g.lTH, g.lTW, g.lG, pl.npos, 256 / pl.mw, 0, 0, g.tiles_h, g.tiles_w, (int)grid.x,
+                       (int)grid.y, (int)grid.z, g.nsplit, g.chunks_per_split, 0, stats ? 1 : 0});
+}
+
 // `dst` = final output when nsplit == 1, else the partial slabs [nsplit][N,M,Ho,Wo]
 template <int MODE>
 int launch_tapconv(const float* in, const float* wp, const float* bias, float* dst, const TapPlan& pl, hipStream_t s,
@@ -1595,6 +1607,8 @@ int launch_tapconv(const float* in, const float* wp, const float* bias, float* d
                                     (double)TC::NT * g.K * g.M);
         GxProf pf(MODE == M_C5 ? KID_DCONV : KID_TAPCONV_C3 + MODE, s, flops, bytes);
         gx_tapconv_note(pl.b1 ? 3 : 0);
+        note_tap_plan(MODE == M_C3 ? GX_PLAN_TAP_C3 : (MODE == M_DG ? GX_PLAN_TAP_DG : (MODE == M_C5 ? GX_PLAN_TAP_C5 : GX_PLAN_TAP_DT)),
+                      pl, pl.grid, false);
         constexpr int LO = (MODE == M_DG) ? 8 : 2;
         if (pl.npos == LO) launch_tapconv_inst<MODE, LO>(in, wp, bias, dst, pl, s);
         else launch_tapconv_inst<MODE, 2 * LO>(in, wp, bias, dst, pl, s);
@@ -2263,6 +2277,8 @@ static int tap_mode_now() {
 }
 bool gx_tapconv_b1_on(void) { return tap_mode_now() == 3; }
 void gx_tapconv_note(int mode) { t_tap_last = mode; }
+static thread_local GxConvPlan t_conv_plan = {};      // family GX_PLAN_NONE until this thread's first conv launch
+void gx_conv_plan_note(const GxConvPlan& p) { t_conv_plan = p; }
 
 // =================================================================== C ABI
 int gx_defer_flush_wgrad(const GxWgradRed* items, int n, hipStream_t s) {
@@ -2322,6 +2338,11 @@ int gx_tapconv_precision(int mode) {
 }
 int gx_tapconv_precision_get(void) { return tap_mode_now(); }
 int gx_tapconv_last_mode(void) { return t_tap_last; }
+int gx_conv_last_plan(int* out, int n) {
+    const int* f = reinterpret_cast<const int*>(&t_conv_plan);
+    for (int i = 0; out && i < n && i < GX_PLAN_FIELDS; ++i) out[i] = f[i];
+    return GX_PLAN_FIELDS;
+}
 
 // workspace = packed weights (+ split-K partial slabs when the plan splits the reduction)
 static size_t conv3x3_pack_floats(int Cin, int Cout) {
@@ -2480,6 +2501,8 @@ static int conv3x3_fwd_impl(const float* x, const float* w, const float* bias, i
         {
             GxProf pf(KID_TAPCONV_C3, s, 2.0 * N * (double)Cout * Cin * 9 * H * W,
                       4.0 * ((double)N * Cin * H * W + (double)N * Cout * H * W));
+            // (no tile: a thread owns 4 pixels of a row and SC_COB output channels -- 1024 pixels per workgroup)
+            gx_conv_plan_note({GX_PLAN_SMALLCIN, 0, 0, 0, 0, 0, 4 * 256, 0, 0, 0, 0, (int)grid.x, (int)grid.y, (int)grid.z, 1, 0, 0, 0});
             hipLaunchKernelGGL(conv3x3_smallcin_fwd_kernel<4>, grid, dim3(256), 0, s, x, w, bias, act, y, N, Cout, H, W);
         }
         GX_CHECK_LAUNCH("gx_conv3x3_fwd(small Cin)");
@@ -3023,14 +3046,18 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
         dim3 grid(p0.grid.x, p0.grid.y * 2, p0.grid.z);
         ConvGeom gg = p0.g;
         gg.zeros = !b1 ? zero_page(s) : nullptr;
+        // output statistics in the epilogue: 256-pixel tiles of one image, no channel split, 8-channel blocks (fp32 form: the
+        // LDS-DMA kernel only, i.e. with the zero page)
+        const bool st_ok = stats && p0.mw == 1 && p0.npos == 2 && gg.nsplit == 1 && gg.lG == 0 && (Cout % 8) == 0 && (b1 || gg.zeros);
+        if (st_ok) {
+            gg.stats = stats;
+            gg.stats_parts = gg.tiles_h * gg.tiles_w * 2;
+            if (stats_parts_out) *stats_parts_out = gg.stats_parts;
+        }
+        note_tap_plan(GX_PLAN_TAP_DT, p0, grid, st_ok);      // (gx_conv_last_plan: the grid and the decision the launch below uses)
         if (b1) {             // one bf16 piece per operand: register staging (the input is converted on its way into LDS)
-            const bool st_ok = stats && p0.mw == 1 && p0.npos == 2 && gg.nsplit == 1 && gg.lG == 0 && (Cout % 8) == 0;
-            if (st_ok) {
-                gg.stats = stats;
-                gg.stats_parts = gg.tiles_h * gg.tiles_w * 2;
-                if (stats_parts_out) *stats_parts_out = gg.stats_parts;
-                launch_dt<2, false, 1, true, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
-            } else if (p0.mw == 2) {
+            if (st_ok) launch_dt<2, false, 1, true, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+            else if (p0.mw == 2) {
                 if (p0.npos == 2) launch_dt<2, false, 2, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
                 else launch_dt<4, false, 2, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
             } else if (p0.npos == 2) launch_dt<2, false, 1, false, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
@@ -3040,14 +3067,8 @@ static int deconv_fwd_impl(const float* x, const float* w, const float* bias, fl
             if (p0.npos == 2) launch_dt<2, false, 2>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
             else launch_dt<4, false, 2>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
         } else if (gg.zeros) {
-            // output statistics in the epilogue: one image per tile, no channel split, 8-channel blocks
-            const bool st_ok = stats && p0.npos == 2 && gg.nsplit == 1 && gg.lG == 0 && (Cout % 8) == 0;
-            if (st_ok) {
-                gg.stats = stats;
-                gg.stats_parts = gg.tiles_h * gg.tiles_w * 2;
-                if (stats_parts_out) *stats_parts_out = gg.stats_parts;
-                launch_dt<2, true, 1, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
-            } else if (p0.npos == 2) launch_dt<2, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+            if (st_ok) launch_dt<2, true, 1, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
+            else if (p0.npos == 2) launch_dt<2, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
             else launch_dt<4, true>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);
         } else {
             if (p0.npos == 2) launch_dt<2, false>(grid, p0.lds_bytes, s, x, wpu0, wpu1, bias, dst, gg);

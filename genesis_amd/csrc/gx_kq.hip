@@ -1012,6 +1012,14 @@ int q_split_tail(int ptiles, int M, unsigned* grid_x) {
     return nfull;
 }
 
+// the record of a launch of this file (gx_conv_last_plan): from the geometry and the grid the kernel is handed.  form: 0 fp32,
+// 1 six bf16 piece products, 2 three fp16 piece products, 3 one bf16 piece
+void q_note(int family, int form, const QGeom& g, int nq, dim3 grid) {
+    const int pixels = g.rt_th ? g.rt_th * g.rt_tw : 1 << (g.lTH + g.lTW + g.lG);
+    gx_conv_plan_note({family, form, g.lTH, g.lTW, g.lG, nq, pixels, g.rt_th, g.rt_tw, g.tiles_h, g.tiles_w, (int)grid.x, (int)grid.y,
+                       (int)grid.z, 1, g.nchunks, g.nfull, g.stats ? 1 : 0});
+}
+
 int g_kq_mode = 1;    // gx_kq_policy: 0 off, 1 auto (layers whose grid fills the chip), 2 every eligible shape
 
 int kq_mode() { return g_kq_mode; }
@@ -1054,6 +1062,7 @@ int gx_kq_c3_launch(const float* in, const float* wp, const float* bias, int act
         GxProf pf(KID_TAPCONV_C3, s, 2.0 * N * (double)M * K * 9 * H * W,
                   4.0 * ((double)N * K * H * W + (double)N * M * H * W + 9.0 * K * M));
         static bool a3 = false, a4 = false;
+        q_note(GX_PLAN_KQ_C3, 0, g, nq, grid);
         if (nq == 3) { q_set_attr(&kq_kernel<Q_C3, 3>, &a3); hipLaunchKernelGGL((kq_kernel<Q_C3, 3>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
         else { q_set_attr(&kq_kernel<Q_C3, 4>, &a4); hipLaunchKernelGGL((kq_kernel<Q_C3, 4>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
     }
@@ -1080,6 +1089,7 @@ int gx_kq_deconv_fwd_launch(const float* in, const float* wp0, const float* wp1,
         GxProf pf(KID_TAPCONV_DT0, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * Hb * Wb + (double)N * M * 4 * Hb * Wb + 25.0 * K * M));
         static bool a[4] = {false, false, false, false};
+        q_note(GX_PLAN_KQ_DT, 0, g, nq, grid);
         if (nq == 3 && st) { q_set_attr(&kq_dt_kernel<3, true>, &a[0]); hipLaunchKernelGGL((kq_dt_kernel<3, true>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
         else if (nq == 3) { q_set_attr(&kq_dt_kernel<3, false>, &a[1]); hipLaunchKernelGGL((kq_dt_kernel<3, false>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
         else if (st) { q_set_attr(&kq_dt_kernel<4, true>, &a[2]); hipLaunchKernelGGL((kq_dt_kernel<4, true>), grid, dim3(256), lds, s, in, wp0, wp1, bias, out, g); }
@@ -1243,6 +1253,7 @@ int gx_kq_deconv_fwd_h_launch(const float* in, const float* wp0, const float* wp
         GxProf pf(KID_KQ_DTH, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * Hb * Wb + (double)N * M * 4 * Hb * Wb + 25.0 * K * M));
         static bool a[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
+        q_note(GX_PLAN_KQ_DTH, amax_ws ? 2 : (b1 ? 3 : 1), g, nq, grid);
         if (amax_ws) {          // fp16 x 3: the input's amax (one small launch ahead of this one, outside its profiling record)
             g.x_amax = x_parts ? x_parts : amax_ws;
             if (x_parts) g.x_amax_n = x_nparts;
@@ -1326,6 +1337,7 @@ int gx_kq_c3h_launch(const float* in, const float* wp, const float* bias, int ac
         GxProf pf(KID_KQ_C3H, s, 2.0 * N * (double)M * K * 9 * H * W,
                   4.0 * ((double)N * K * H * W + (double)N * M * H * W + 9.0 * K * M));
         static bool a3 = false, a4 = false, f3 = false, f4 = false, b3 = false, b4 = false;
+        q_note(GX_PLAN_KQ_C3H, amax_ws ? 2 : (b1 ? 3 : 1), g, nq, grid);
         if (b1) {
             if (nq == 3) { q_set_attr(&kq_c3h_kernel<3, PF_B1>, &b3); hipLaunchKernelGGL((kq_c3h_kernel<3, PF_B1>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
             else { q_set_attr(&kq_c3h_kernel<4, PF_B1>, &b4); hipLaunchKernelGGL((kq_c3h_kernel<4, PF_B1>), grid, dim3(256), lds, s, in, wp, bias, out, g); }
@@ -1387,6 +1399,7 @@ int gx_kq_c5h_launch(const float* in, const float* wp, float* out, int N, int K,
     {
         GxProf pf(KID_KQ_C5H, s, 2.0 * N * (double)M * K * 25 * H * W, 4.0 * ((double)N * K * H * W + (double)N * M * H * W + 25.0 * K * M));
         static bool a4 = false, f4 = false, b4 = false;
+        q_note(GX_PLAN_KQ_C5H, amax_ws ? 2 : (b1 ? 3 : 1), g, 4, grid);      // (kq_c5h_kernel<4, ...>: always four staging rounds)
         if (b1) {
             q_set_attr(&kq_c5h_kernel<4, PF_B1>, &b4);
             hipLaunchKernelGGL((kq_c5h_kernel<4, PF_B1>), grid, dim3(256), lds, s, in, wp, out, g);
@@ -1425,6 +1438,7 @@ int gx_kq_deconv_dgrad_h_launch(const float* dy, const float* wp, float* dx, int
         GxProf pf(KID_KQ_DGH, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * 4 * Hb * Wb + (double)N * M * Hb * Wb + 25.0 * K * M));
         static bool a3 = false, a4 = false, f3 = false, f4 = false, b3 = false, b4 = false;
+        q_note(GX_PLAN_KQ_DGH, amax_ws ? 2 : (b1 ? 3 : 1), g, nq, grid);
         if (b1) {
             if (nq == 3) { q_set_attr(&kq_dgh_kernel<3, PF_B1>, &b3); hipLaunchKernelGGL((kq_dgh_kernel<3, PF_B1>), grid, dim3(256), lds, s, dy, wp, dx, g); }
             else { q_set_attr(&kq_dgh_kernel<4, PF_B1>, &b4); hipLaunchKernelGGL((kq_dgh_kernel<4, PF_B1>), grid, dim3(256), lds, s, dy, wp, dx, g); }
@@ -1453,6 +1467,7 @@ int gx_kq_deconv_dgrad_launch(const float* dy, const float* wp, float* dx, int N
         GxProf pf(KID_TAPCONV_DG, s, 2.0 * N * (double)M * K * 25 * Hb * Wb,
                   4.0 * ((double)N * K * 4 * Hb * Wb + (double)N * M * Hb * Wb + 25.0 * K * M));
         static bool a3 = false, a4 = false;
+        q_note(GX_PLAN_KQ_DG, 0, g, nq, grid);
         if (nq == 3) { q_set_attr(&kq_kernel<Q_DG, 3>, &a3); hipLaunchKernelGGL((kq_kernel<Q_DG, 3>), grid, dim3(256), lds, s, dy, wp, nullptr, dx, g); }
         else { q_set_attr(&kq_kernel<Q_DG, 4>, &a4); hipLaunchKernelGGL((kq_kernel<Q_DG, 4>), grid, dim3(256), lds, s, dy, wp, nullptr, dx, g); }
     }

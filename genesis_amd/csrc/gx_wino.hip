@@ -889,17 +889,21 @@ static int wino_launch(const float* in, const float* in2, int K1, const float* U
         if (h) { g_wino_flops_all += flops; if (f16) g_wino_flops_f16 += flops; }
         const double bytes = 4.0 * ((double)N * K * H * W + (double)N * M * H * W + 9.0 * K * M);
         GxProf pf(KID_WINO, s, flops, bytes);
+        const dim3 grid(N * g.tiles_h * g.tiles_w, g.Mpad / 64);
+        // gx_conv_last_plan: one image per workgroup tile of 2 WTH x 2 WTW output pixels, Kpad / (HKC | WKC) channel chunks
+        gx_conv_plan_note({GX_PLAN_WINO, !h ? 0 : (b1 ? 3 : (f16 ? 2 : 1)), 0, 0, 0, 0, 2 * WTH * 2 * WTW, 0, 0, g.tiles_h, g.tiles_w,
+                           (int)grid.x, (int)grid.y, (int)grid.z, 1, g.Kpad / (h ? HKC : WKC), 0, 0});
         if (h && b1)
-            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B1>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B1>), grid, dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else if (h && f16)
-            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_F3>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_F3>), grid, dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else if (h)
-            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B6>), dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2,
+            hipLaunchKernelGGL((wino_conv_h_kernel<1, WPF_B6>), grid, dim3(256), lds, s, in, in2,
                                reinterpret_cast<const unsigned*>(U), out, out2, g);
         else
-        hipLaunchKernelGGL(wino_conv_kernel, dim3(N * g.tiles_h * g.tiles_w, g.Mpad / 64), dim3(256), lds, s, in, in2, U,
+        hipLaunchKernelGGL(wino_conv_kernel, grid, dim3(256), lds, s, in, in2, U,
                            out, out2, g);
     }
     GX_CHECK_LAUNCH("winograd conv3x3");

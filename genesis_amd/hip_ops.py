@@ -283,6 +283,26 @@ def defer_discard():
     del defer_state().keep[:]
 
 
+# ------------------------------------------------------------------ the tile plan of the last conv launch (gx_conv_last_plan)
+PLAN_FIELDS = ('family', 'form', 'lTH', 'lTW', 'lG', 'nq', 'pixels', 'rt_th', 'rt_tw', 'tiles_h', 'tiles_w', 'grid_x', 'grid_y',
+               'grid_z', 'nsplit', 'chunks_per_split', 'nfull', 'stats')          # the GX_PLAN_* indices of include/genesis_hip.h
+PLAN_FAMILIES = ('none', 'tap_c3', 'tap_dt', 'tap_dg', 'tap_c5', 'kq_c3', 'kq_dt', 'kq_dg', 'kq_c3h', 'kq_dth', 'kq_dgh', 'kq_c5h',
+                 'wino', 'smallcin')                                              # GX_PLAN_NONE ... GX_PLAN_SMALLCIN
+PLAN_FORMS = ('fp32', 'bf16x6', 'fp16x3', 'bf16x1')
+
+
+def conv_last_plan():
+    """The tile plan of this thread's last forward / data-gradient conv launch as a dict (family and form by name, the rest
+    integers; family 'none' before any launch).  Host state only: needs no GPU and does not synchronise."""
+    buf = (ctypes.c_int * len(PLAN_FIELDS))()
+    n = int(_lib.load().gx_conv_last_plan(buf, len(PLAN_FIELDS)))
+    assert n == len(PLAN_FIELDS), 'gx_conv_last_plan has %d fields, hip_ops.PLAN_FIELDS %d' % (n, len(PLAN_FIELDS))
+    plan = dict(zip(PLAN_FIELDS, (int(v) for v in buf)))
+    plan['family'] = PLAN_FAMILIES[plan['family']]
+    plan['form'] = PLAN_FORMS[plan['form']]
+    return plan
+
+
 # ------------------------------------------------------------------ conv3x3
 def conv3x3_fwd(x, w, amax_in=None):
     _chk(x, 'conv3x3_fwd.x'); _chk(w, 'conv3x3_fwd.w')

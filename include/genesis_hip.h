@@ -159,6 +159,48 @@ int gx_matmul_precision_get(void);
 int gx_tapconv_precision(int mode);
 int gx_tapconv_precision_get(void);
 int gx_tapconv_last_mode(void);
+/*      gx_conv_last_plan(out, n): the tile plan of this thread's most recent forward / data-gradient conv launch (the tap-conv
+ *      kernels, the input-layer kernel of gx_conv3x3_fwd, every gx_kq.hip conv kernel, Winograd), written by the launcher on the
+ *      host just before it launches, every field copied from the values the launch itself uses.  Fills out[0 .. min(n,
+ *      GX_PLAN_FIELDS)) in the order of the GX_PLAN_* indices below and returns GX_PLAN_FIELDS; before any such launch the family
+ *      is GX_PLAN_NONE and every other field 0.  A field the family does not have is 0.  Helper launches (weight packing, amax
+ *      passes, split-K reduces) leave the record alone.  For tests and diagnosis: no synchronisation, no device work. */
+#define GX_PLAN_FIELDS 18
+/*      out[] indices */
+#define GX_PLAN_FAMILY 0          /* GX_PLAN_NONE ... GX_PLAN_SMALLCIN */
+#define GX_PLAN_FORM 1            /* operands: 0 fp32, 1 bf16 x 6, 2 fp16 x 3, 3 bf16 x 1 */
+#define GX_PLAN_LTH 2             /* log2 of the tile's height, width and images per tile */
+#define GX_PLAN_LTW 3
+#define GX_PLAN_LG 4
+#define GX_PLAN_NQ 5              /* gx_kq.hip: staging rounds nq (3 / 4); tap conv: the template's NPOS */
+#define GX_PLAN_PIXELS 6          /* pixels per tile */
+#define GX_PLAN_RT_TH 7           /* whole-row tiles (kq C3H), else 0 */
+#define GX_PLAN_RT_TW 8
+#define GX_PLAN_TILES_H 9
+#define GX_PLAN_TILES_W 10
+#define GX_PLAN_GRID_X 11
+#define GX_PLAN_GRID_Y 12
+#define GX_PLAN_GRID_Z 13
+#define GX_PLAN_NSPLIT 14         /* split-K slabs (1: none) and 8- / 16-channel chunks per slab */
+#define GX_PLAN_CHUNKS 15
+#define GX_PLAN_NFULL 16          /* gx_kq.hip: whole-tile workgroups (q_split_tail) / tiles of the persistent loop */
+#define GX_PLAN_STATS 17          /* 1: the GroupNorm statistics epilogue ran */
+/*      families */
+#define GX_PLAN_NONE 0
+#define GX_PLAN_TAP_C3 1          /* tapconv_kernel<M_C3> */
+#define GX_PLAN_TAP_DT 2          /* tapconv_dt_kernel (both row parities of the transposed conv) */
+#define GX_PLAN_TAP_DG 3          /* tapconv_kernel<M_DG> */
+#define GX_PLAN_TAP_C5 4          /* tapconv_kernel<M_C5> */
+#define GX_PLAN_KQ_C3 5           /* kq_kernel<Q_C3> */
+#define GX_PLAN_KQ_DT 6           /* kq_dt_kernel */
+#define GX_PLAN_KQ_DG 7           /* kq_kernel<Q_DG> */
+#define GX_PLAN_KQ_C3H 8          /* kq_c3h_kernel */
+#define GX_PLAN_KQ_DTH 9          /* kq_dth_kernel */
+#define GX_PLAN_KQ_DGH 10         /* kq_dgh_kernel */
+#define GX_PLAN_KQ_C5H 11         /* kq_c5h_kernel */
+#define GX_PLAN_WINO 12           /* wino_conv_kernel / wino_conv_h_kernel */
+#define GX_PLAN_SMALLCIN 13       /* conv3x3_smallcin_fwd_kernel */
+int gx_conv_last_plan(int* out, int n);
 /*      Mode 2's per-tensor maximum without a second pass over the tensor: gx_kq_amax_link(parts, capacity, numel) arms a one-shot,
  *      per-thread hand-over -- the next producer that supports it (the register-resident GroupNorm + ReLU kernels behind gx_gn_relu_fwd_parts /
  *      gx_gn_relu_bwd_parts and the decoder head's backward behind gx_gn_relu_bwd_proj: models/genesisv2_config.py:90-99) writes one partial maximum of the gradient it stores
