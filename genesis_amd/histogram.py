@@ -9,7 +9,7 @@ writer is what tensorboardX's make_histogram would put into its HistogramProto, 
 >= 1.7 and torch.utils.tensorboard both have it; it writes the event add_histogram would).
 
 Not here: `max_bins`, numpy's string bin rules and integer bin counts, host tensors, non-contiguous tensors, other dtypes than
-fp32 / fp64 (all refused by name); a TensorBoard event-file writer."""
+fp32 / fp64 (all refused by name).  The event-file writer: genesis_amd/tbwriter.py."""
 import collections
 import ctypes
 

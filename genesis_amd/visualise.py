@@ -7,8 +7,10 @@ Every grid of a forward pass is written by ONE gx_vis_compose launch (include/ge
 read in place for exp and argmax, the padding written by the same launch -- and the atlas comes to the host in ONE copy; the
 arrays handed to the writer are views of it (the int64 colour grids: exact conversions of such views).
 
-Not here: a TensorBoard event-file writer, make_grid's normalize / scale_each, scripts/visualise_data.py (add_histogram
-logging: genesis_amd/histogram.py)."""
+A writer with `add_images_device` (genesis_amd/tbwriter.py) is handed the atlas's device views instead: the pictures are packed for
+their PNGs on the device and come to the host as bytes.
+
+Not here: make_grid's normalize / scale_each, scripts/visualise_data.py (add_histogram logging: genesis_amd/histogram.py)."""
 import ctypes
 import json
 import os.path as osp
@@ -223,6 +225,10 @@ class _Atlas(object):
         self.host = self.run().cpu()
         return int(self.host[self.words:].view(torch.int32)[0]) & 0xffffffff
 
+    def fetch_overflow(self):
+        """run(), then only the overflow counter comes to the host (4 bytes); the pictures stay on the device for view()."""
+        return int(self.run()[self.words:].view(torch.int32).cpu()[0]) & 0xffffffff
+
     def host_view(self, pic):
         return self.view(pic, self.host)
 
@@ -283,13 +289,20 @@ def colour_seg_masks(masks, palette='15'):
 
 # ---- visualise_outputs ---------------------------------------------------------------------------------------------------------
 def _log_pictures(atlas, writer, calls, iter_idx, palette_size):
-    """Fetches the atlas and makes the recorded writer calls, in order."""
+    """Fetches the atlas and makes the recorded writer calls, in order.  A writer that packs pictures on the device
+    (genesis_amd.tbwriter: add_images_device) gets the atlas's device views in one call instead, and only the overflow count
+    comes to the host here."""
     if not calls:
         return
-    overflow = atlas.fetch()
+    on_device = hasattr(writer, 'add_images_device')
+    overflow = atlas.fetch_overflow() if on_device else atlas.fetch()
     if overflow:
         raise GenesisHipError('visualise_outputs: %d pixels carry a label or mask index outside the palette of %d colours; '
                               'pass a larger palette' % (overflow, palette_size))
+    if on_device:
+        writer.add_images_device([(tag, atlas.view(pic).to(torch.int64) if colour else atlas.view(pic), 'CHW')
+                                  for tag, pic, colour in calls], iter_idx)
+        return
     for tag, pic, colour in calls:
         array = atlas.host_view(pic)
         writer.add_image(tag, array.to(torch.int64) if colour else array, iter_idx)

@@ -1111,6 +1111,64 @@ int gx_hist_multi(const long long* table_host, const long long* table_dev, long 
                   const double* edges, int n_edges, unsigned int* counts, double* stats, unsigned long long* tally, void* ws,
                   size_t ws_bytes, gx_stream_t stream);
 
+/* ---- the device side of the TensorBoard event-file writer (genesis_amd/tbwriter.py: the import replacement of the reference's
+ *      `from tensorboardX import SummaryWriter`, train.py:28).
+ *      gx_scalar_snapshot: tensorboardX's add_scalar reads a device scalar with one blocking copy per call.  This copies n <=
+ *      GX_SCALAR_MAX_REFS one-element device values, in stream order, into ring[first_slot .. first_slot + n) as fp64, one thread per
+ *      value, by ONE launch.  `refs` is a HOST structure: its (address, dtype) pairs travel by value in the kernel arguments, so
+ *      nothing is uploaded and the call never waits for the device.  dtype: GX_SCALAR_FP32 / _FP64 / _I32 / _I64 (an int64 beyond
+ *      2^53 is rounded to the nearest double).  ring: fp64 [ring_slots] on the device, 8-byte aligned.
+ *      GX_EINVAL before the launch: a null pointer, n outside [1, GX_SCALAR_MAX_REFS], an unknown dtype, an address that is null or
+ *      not aligned to its element, slots outside the ring.
+ *      gx_png_pack: ONE launch turns n_pictures pictures into the byte streams that zlib deflates for their PNGs.  Per picture
+ *      H (1 + W C) bytes at out + DST: per row the filter-type byte, then the W C filtered bytes.  The descriptors,
+ *      GX_PNGPACK_DESC_WORDS int64 words each, form one table of table_words words that the caller holds twice with the same
+ *      contents: table_host is validated here before anything is launched, table_dev is what the kernel reads.  Descriptor words
+ *      (GX_PNGPACK_D_*):
+ *        SRC         device address of element (0, 0, 0), aligned to its element
+ *        KIND        GX_PNGPACK_FP32: byte = trunc(clamp(x, 0, 1) * 255.0f), the product in fp32, NaN -> 0 (for x in [0, 1] what
+ *                    tensorboardX publishes: (x * 255.0).astype(uint8));  GX_PNGPACK_U8: the byte itself;  GX_PNGPACK_I64: the value
+ *                    clamped to 0..255
+ *        C, H, W     C = 1 (grey, colour type 0) or 3 (RGB, colour type 2); 1 <= H, W <= GX_PNGPACK_MAX_DIM
+ *        PIX_STRIDE, ROW_STRIDE, CH_STRIDE   in elements: pixel (y, x), channel c is element y ROW_STRIDE + x PIX_STRIDE +
+ *                    c CH_STRIDE, so CHW (1, W, H W) and HWC (C, W C, 1) are read by the same kernel
+ *        DST         byte offset of the picture's stream in out = sum over the pictures before it of H (1 + W C)
+ *        ROW0        first global row of the picture = sum over the pictures before it of H
+ *      The work item is one row, one wave per row.  The bytes of the row and of the row above are both derived from the source
+ *      (row -1 and pixel -1 are zero), so rows are independent.  All five filters are computed (None, Sub with bpp = C, Up,
+ *      Average = floor((a + b) / 2), Paeth with ties in the order a, b, c); the one with the smallest sum over the row of
+ *      |filtered byte as a signed byte| is written, ties to the lowest filter number.
+ *      GX_EINVAL before the launch: a null pointer, n_pictures < 1, a table shorter than its descriptors, an unknown KIND, C not 1
+ *      or 3, H or W outside [1, GX_PNGPACK_MAX_DIM], a SRC that is null or not aligned, a stride below 1, DST or ROW0 that disagree
+ *      with their prefixes, streams that do not fit out_bytes. */
+#define GX_SCALAR_FP32 0
+#define GX_SCALAR_FP64 1
+#define GX_SCALAR_I32 2
+#define GX_SCALAR_I64 3
+#define GX_SCALAR_MAX_REFS 32
+typedef struct {
+    const void* ptr[GX_SCALAR_MAX_REFS];
+    int dtype[GX_SCALAR_MAX_REFS];
+} gx_scalar_refs;
+int gx_scalar_snapshot(const gx_scalar_refs* refs, int n, double* ring, int ring_slots, int first_slot, gx_stream_t stream);
+#define GX_PNGPACK_FP32 0
+#define GX_PNGPACK_U8 1
+#define GX_PNGPACK_I64 2
+#define GX_PNGPACK_D_SRC 0
+#define GX_PNGPACK_D_KIND 1
+#define GX_PNGPACK_D_C 2
+#define GX_PNGPACK_D_H 3
+#define GX_PNGPACK_D_W 4
+#define GX_PNGPACK_D_PIX_STRIDE 5
+#define GX_PNGPACK_D_ROW_STRIDE 6
+#define GX_PNGPACK_D_CH_STRIDE 7
+#define GX_PNGPACK_D_DST 8
+#define GX_PNGPACK_D_ROW0 9
+#define GX_PNGPACK_DESC_WORDS 12
+#define GX_PNGPACK_MAX_DIM 4096
+int gx_png_pack(const long long* table_host, const long long* table_dev, long long table_words, int n_pictures, unsigned char* out,
+                long long out_bytes, gx_stream_t stream);
+
 /* ---- FID on the device (scripts/compute_fid.py + third_party/pytorch_fid; genesis_amd/fid.py): pytorch_fid's FID Inception
  *      (Inception-v3, BatchNorm folded into the conv weights by the caller) on NHWC fp32 activations, and the moments of its
  *      features.  Every output's reduction order is fixed by the layer shape alone (no split-K, no atomics), so an image's
