@@ -1197,6 +1197,34 @@ int gx_fid_conv_bias_relu(const float* x, int B, int H, int W, int Cin, const fl
 int gx_fid_pool(const float* x, int B, int H, int W, int C, int mode, float* y, int y_ctot, int y_c0, gx_stream_t stream);
 int gx_fid_moments(const float* feats, int B, int D, double* sum, double* sumsq, gx_stream_t stream);
 
+/* ---- sample quality beside FID (genesis_amd/sample_quality.py; gx_manifold.hip): the all-pairs work of improved precision /
+ *      recall (Kynkaanniemi et al. 2019), density / coverage (Naeem et al. 2020) and KID (Binkowski et al. 2018) over fp32
+ *      feature rows [rows, D], in fp64, with no rows x rows matrix in memory.  D is a multiple of 4 in [4, 8192]; feature
+ *      pointers and workspaces are 16-byte aligned; at most 2^21 rows per operand.
+ *      d2(a, b) = sum_d (a_d - b_d)^2: each feature converted to fp64, the difference formed first, the terms added by one
+ *      fma chain over d = 0 .. D-1.  The order depends on D alone, so d2(a, b) has the same bits in every launch, at every
+ *      tile position and in either argument order, and identical rows give exactly 0: exact ties compare as <=.
+ *      gx_knn_radii: radii2[i] = the k-th smallest of {d2(x_i, x_j) : j != i} (self excluded by index, duplicates counted
+ *      with multiplicity, no square root), X [N, D], 1 <= k <= 8, k <= N - 1; ws of gx_knn_radii_ws_bytes(N, k) bytes
+ *      (ceil(N / 64) k N doubles: the k smallest of every 64-column tile, merged by a second launch).
+ *      gx_manifold_counts: hits[j] = #{i : d2(q_j, r_i) <= radii2[i]} for Q [M, D] against R [N, D] with the radii of R's
+ *      rows; covered[i] = 1 if any j satisfies that inequality for i, else 0.  Both outputs are written in full (cleared by
+ *      the call; int32 atomics, whose result does not depend on order).  (Q = generated, R = real) gives precision
+ *      (hits > 0), density (sum hits) and coverage (covered); (Q = real, R = generated) gives recall.
+ *      gx_kid_sums: for each of S subsets s of m rows, x_a = X[ix[s m + a]] (X [NX, D]) and y_b = Y[iy[s m + b]] (Y [NY, D]),
+ *      with kappa(x, y) = (x . y / D + 1)^3: sums[s] = (sum_{a != b} kappa(x_a, x_b), sum_{a != b} kappa(y_a, y_b),
+ *      sum_{a, b} kappa(x_a, y_b)).  ix / iy are device int32 [S, m] that the caller has checked against [0, NX) / [0, NY)
+ *      (the kernel clamps an index into the range instead of reading outside).  2 <= m <= 65536, 1 <= S <= 21845; ws of
+ *      gx_kid_sums_ws_bytes(m, S) bytes.  Fixed summation order, no floating-point atomics: a repeat gives the same bits.
+ *      The *_ws_bytes queries return 0 for arguments the calls refuse.  Non-finite features give unspecified values. */
+size_t gx_knn_radii_ws_bytes(int N, int k);
+int gx_knn_radii(const float* X, int N, int D, int k, double* radii2, void* ws, size_t ws_bytes, gx_stream_t stream);
+int gx_manifold_counts(const float* Q, int M, const float* R, int N, int D, const double* radii2, int* hits, int* covered,
+                       gx_stream_t stream);
+size_t gx_kid_sums_ws_bytes(int m, int S);
+int gx_kid_sums(const float* X, int NX, const int* ix, const float* Y, int NY, const int* iy, int m, int D, int S, double* sums,
+                void* ws, size_t ws_bytes, gx_stream_t stream);
+
 /* ---- input feeder (datasets/multid_config.py:131-135 ToTensor + F.interpolate(size), multi_object_config.py:176-186):
  *      uint8 frames [B, Hs, Ws, C] (HWC, as stored) -> fp32 [B, C, H, W] = value / 255, nearest-neighbour resampled to
  *      H x W when the stored size differs (F.interpolate's default mode).  Bit-exact against the torch ops. */
