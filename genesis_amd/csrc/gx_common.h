@@ -77,6 +77,11 @@ int gx_defer_flush_gn(const GxGnRed* items, int n, hipStream_t s);         // gx
 // ---- PNG frames (gx_png.cpp, gx_png.hip): the largest width and height.  gx_png_unfilter hands the last row of a band to the
 // next band through kGxPngMaxDim * C bytes of LDS (16 KB for RGBA); the host checks reject larger frames with this same constant.
 constexpr int kGxPngMaxDim = 4096;
+// ---- loose image files (gx_jpeg.cpp's _any entry points, gx_imagefile.hip): the largest width and height of a frame of either
+// format, the PNG bound above
+constexpr int kGxImageMaxDim = kGxPngMaxDim;
+// Upper bound on the source rows (columns) that R consecutive output rows of Pillow's BILINEAR table of in -> out span (gx_feed.hip)
+int gx_pil_band_rows(int in, int out, int R);
 
 static inline int gx_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int gx_ceil_div(int a, int b) { return (a + b - 1) / b; }

@@ -274,6 +274,8 @@ int gx_u8hwc_to_f32chw(const unsigned char* src, float* dst, int B, int Hs, int 
 
 }  // extern "C"
 
+int gx_pil_band_rows(int in, int out, int R) { return pil_band_rows(in, out, R); }      // gx_common.h: for gx_imagefile.hip
+
 extern "C" {
 
 int gx_pil_bilinear_ksize(int in, int out) {

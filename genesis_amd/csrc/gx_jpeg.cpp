@@ -4,6 +4,10 @@
 // functions, no HIP calls: they work without a GPU, as gx_tfrecord.cpp does.
 //   accepted  SOF0, 8-bit samples, three components in one interleaved scan, luma 1x1 / 2x1 / 2x2 with chroma 1x1,
 //             8-bit quantisation tables, any DHT tables, DRI with RSTn markers; APPn and COM are skipped
+//   _any      the entry points of the ragged decoder (gx_imagefile.hip, genesis_amd/imagefile.py) share every line of the
+//             marker walk and the Huffman code with the two above; they differ in two limits only: frames up to
+//             kGxImageMaxDim on a side instead of 128, and one-component (greyscale) streams, whose single plane is
+//             padded to whole 8 x 8 blocks
 //   output    per component the blocks of its padded plane (whole MCUs) in raster order, each block 64 QUANTISED int16
 //             coefficients in natural (row-major) order with the DC prediction undone; coefficient x quantiser does
 //             not fit int16, so the kernel multiplies
@@ -15,7 +19,7 @@
 
 namespace {
 
-constexpr int kMaxDim = 128;           // the device kernel's frame limit (three planes in LDS)
+constexpr int kMaxDim = 128;           // gx_jpeg_decode_f32chw's frame limit (three planes in LDS)
 constexpr int kLook = 9;               // bits of the Huffman lookahead table
 
 const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -33,6 +37,7 @@ struct Huff {
 
 struct Frame {
     int width, height, sampling, hs, vs, mcux, mcuy, restart;
+    int ncomp;                         // 3, or 1 (greyscale: the _any entry points only)
     int comp_id[3], comp_tq[3];
     int blocks_w[3], blocks_h[3];
     bool have_sof;
@@ -46,6 +51,8 @@ struct Parser {
     Huff dc[4], ac[4];
     Frame f;
     int scan_td[3], scan_ta[3];
+    int max_dim;                       // kMaxDim, or kGxImageMaxDim for the _any entry points
+    bool grey_ok;
 };
 
 int fail(const char* what) {
@@ -130,18 +137,19 @@ int parse_sof0(Parser* s, size_t at, size_t len) {
     f.height = (d[1] << 8) | d[2];
     f.width = (d[3] << 8) | d[4];
     const int nf = d[5];
-    if (nf == 1) return fail("greyscale (one component) is not supported");
+    if (nf == 1 && !s->grey_ok) return fail("greyscale (one component) is not supported");
     if (nf == 4) return fail("four components (CMYK / YCCK) are not supported");
-    if (nf != 3) return fail("bad component count");
-    if (len < 6 + 3 * 3) return fail("the stream ends early (inside the frame header)");
+    if (nf != 3 && nf != 1) return fail("bad component count");
+    if (len < 6 + 3 * (size_t)nf) return fail("the stream ends early (inside the frame header)");
     if (f.width <= 0 || f.height <= 0) return fail("empty frame");
-    if (f.width > kMaxDim || f.height > kMaxDim) {
-        gx_set_error("gx_jpeg: a %d x %d frame is larger than the %d x %d the device kernel decodes", f.width, f.height, kMaxDim,
-                     kMaxDim);
+    if (f.width > s->max_dim || f.height > s->max_dim) {
+        gx_set_error("gx_jpeg: a %d x %d frame is larger than the %d x %d the device kernel decodes", f.width, f.height, s->max_dim,
+                     s->max_dim);
         return GX_EDATA;
     }
-    int h[3], v[3];
-    for (int c = 0; c < 3; ++c) {
+    f.ncomp = nf;
+    int h[3] = {1, 1, 1}, v[3] = {1, 1, 1};
+    for (int c = 0; c < nf; ++c) {
         f.comp_id[c] = d[6 + 3 * c];
         h[c] = d[7 + 3 * c] >> 4;
         v[c] = d[7 + 3 * c] & 15;
@@ -149,7 +157,10 @@ int parse_sof0(Parser* s, size_t at, size_t len) {
         if (f.comp_tq[c] > 3) return fail("bad quantisation table selector");
     }
     const bool chroma11 = h[1] == 1 && v[1] == 1 && h[2] == 1 && v[2] == 1;
-    if (chroma11 && h[0] == 1 && v[0] == 1) f.sampling = 0;
+    if (nf == 1) {                     // a single component is never interleaved: its blocks are 8 x 8 whatever its factors say
+        h[0] = v[0] = 1;
+        f.sampling = 0;
+    } else if (chroma11 && h[0] == 1 && v[0] == 1) f.sampling = 0;
     else if (chroma11 && h[0] == 2 && v[0] == 1) f.sampling = 1;
     else if (chroma11 && h[0] == 2 && v[0] == 2) f.sampling = 2;
     else {
@@ -163,8 +174,8 @@ int parse_sof0(Parser* s, size_t at, size_t len) {
     f.mcuy = (f.height + 8 * f.vs - 1) / (8 * f.vs);
     f.blocks_w[0] = f.mcux * f.hs;
     f.blocks_h[0] = f.mcuy * f.vs;
-    f.blocks_w[1] = f.blocks_w[2] = f.mcux;
-    f.blocks_h[1] = f.blocks_h[2] = f.mcuy;
+    f.blocks_w[1] = f.blocks_w[2] = nf == 3 ? f.mcux : 0;
+    f.blocks_h[1] = f.blocks_h[2] = nf == 3 ? f.mcuy : 0;
     f.have_sof = true;
     return GX_OK;
 }
@@ -173,9 +184,10 @@ int parse_sos(Parser* s, size_t at, size_t len) {
     const unsigned char* d = s->p + at;
     if (!s->f.have_sof) return fail("a scan before the frame header");
     if (len < 1) return fail("the stream ends early (inside the scan header)");
-    if (d[0] != 3) return fail("the three components must come in one interleaved scan");
-    if (len < 1 + 2 * 3 + 3) return fail("the stream ends early (inside the scan header)");
-    for (int c = 0; c < 3; ++c) {
+    const int nc = s->f.ncomp;
+    if (d[0] != nc) return fail(nc == 3 ? "the three components must come in one interleaved scan" : "the scan does not hold the frame's one component");
+    if (len < 1 + 2 * (size_t)nc + 3) return fail("the stream ends early (inside the scan header)");
+    for (int c = 0; c < nc; ++c) {
         if (d[1 + 2 * c] != s->f.comp_id[c]) return fail("the scan's components are not the frame's, in order");
         s->scan_td[c] = d[2 + 2 * c] >> 4;
         s->scan_ta[c] = d[2 + 2 * c] & 15;
@@ -183,7 +195,7 @@ int parse_sos(Parser* s, size_t at, size_t len) {
             return fail("the scan names a Huffman table that was not defined");
         if (!s->q_defined[s->f.comp_tq[c]]) return fail("the frame names a quantisation table that was not defined");
     }
-    if (d[7] != 0 || d[8] != 63 || d[9] != 0) return fail("a progressive scan (spectral selection / successive approximation)");
+    if (d[1 + 2 * nc] != 0 || d[2 + 2 * nc] != 63 || d[3 + 2 * nc] != 0) return fail("a progressive scan (spectral selection / successive approximation)");
     return GX_OK;
 }
 
@@ -229,9 +241,9 @@ int parse_headers(Parser* s) {
 void fill_info(const Frame& f, int* info) {
     info[0] = f.width;
     info[1] = f.height;
-    info[2] = 3;
+    info[2] = f.ncomp;
     info[3] = f.sampling;
-    for (int c = 0; c < 3; ++c) info[4 + c] = f.blocks_w[c] * f.blocks_h[c];
+    for (int c = 0; c < 3; ++c) info[4 + c] = f.blocks_w[c] * f.blocks_h[c];      // at most 512 * 512
     info[7] = f.restart;
 }
 
@@ -359,7 +371,7 @@ int decode_scan(Parser* s, short* coef) {
             pred[0] = pred[1] = pred[2] = 0;
         }
         const int my = m / f.mcux, mx = m - my * f.mcux;
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < f.ncomp; ++c) {
             const int ch = c == 0 ? f.hs : 1, cv = c == 0 ? f.vs : 1;
             for (int v = 0; v < cv; ++v)
                 for (int h = 0; h < ch; ++h) {
@@ -374,40 +386,66 @@ int decode_scan(Parser* s, short* coef) {
     return GX_OK;
 }
 
+// the two pairs of entry points differ in the limits only
+int info_entry(const unsigned char* data, size_t len, int* info, int max_dim, bool grey_ok) {
+    Parser s = {};
+    s.p = data;
+    s.n = len;
+    s.max_dim = max_dim;
+    s.grey_ok = grey_ok;
+    const int rc = parse_headers(&s);
+    if (rc == GX_OK) fill_info(s.f, info);
+    return rc;
+}
+
+int decode_entry(const char* name, const unsigned char* data, size_t len, short* coef, size_t coef_capacity, unsigned short* qtab, int* info,
+                 int max_dim, bool grey_ok) {
+    Parser s = {};
+    s.p = data;
+    s.n = len;
+    s.max_dim = max_dim;
+    s.grey_ok = grey_ok;
+    int rc = parse_headers(&s);
+    if (rc == GX_OK) {
+        fill_info(s.f, info);
+        const size_t need = ((size_t)info[4] + info[5] + info[6]) * 64;
+        if (need > coef_capacity) {
+            gx_set_error("%s: the frame needs %zu coefficients, the buffer holds %zu", name, need, coef_capacity);
+            rc = GX_EINVAL;
+        } else {
+            memset(coef, 0, need * sizeof(short));
+            // a grey frame's second and third table are its first: all 192 values are always written
+            for (int c = 0; c < 3; ++c) memcpy(qtab + 64 * c, s.q[s.f.comp_tq[c < s.f.ncomp ? c : 0]], 64 * sizeof(unsigned short));
+            rc = decode_scan(&s, coef);
+        }
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
 
 int gx_jpeg_info(const unsigned char* data, size_t len, int* info) {
     GX_CHECK_ARG(data && info, "gx_jpeg_info: null pointer");
-    Parser s = {};
-    s.p = data;
-    s.n = len;
-    const int rc = parse_headers(&s);
-    if (rc == GX_OK) fill_info(s.f, info);
-    return rc;
+    return info_entry(data, len, info, kMaxDim, false);
 }
 
 int gx_jpeg_entropy_decode(const unsigned char* data, size_t len, short* coef, size_t coef_capacity, unsigned short* qtab,
                            int* info) {
     GX_CHECK_ARG(data && coef && qtab && info, "gx_jpeg_entropy_decode: null pointer");
-    Parser s = {};
-    s.p = data;
-    s.n = len;
-    int rc = parse_headers(&s);
-    if (rc == GX_OK) {
-        fill_info(s.f, info);
-        const size_t need = ((size_t)info[4] + info[5] + info[6]) * 64;
-        if (need > coef_capacity) {
-            gx_set_error("gx_jpeg_entropy_decode: the frame needs %zu coefficients, the buffer holds %zu", need, coef_capacity);
-            rc = GX_EINVAL;
-        } else {
-            memset(coef, 0, need * sizeof(short));
-            for (int c = 0; c < 3; ++c) memcpy(qtab + 64 * c, s.q[s.f.comp_tq[c]], 64 * sizeof(unsigned short));
-            rc = decode_scan(&s, coef);
-        }
-    }
-    return rc;
+    return decode_entry("gx_jpeg_entropy_decode", data, len, coef, coef_capacity, qtab, info, kMaxDim, false);
+}
+
+int gx_jpeg_info_any(const unsigned char* data, size_t len, int* info) {
+    GX_CHECK_ARG(data && info, "gx_jpeg_info_any: null pointer");
+    return info_entry(data, len, info, kGxImageMaxDim, true);
+}
+
+int gx_jpeg_entropy_decode_any(const unsigned char* data, size_t len, short* coef, size_t coef_capacity, unsigned short* qtab,
+                               int* info) {
+    GX_CHECK_ARG(data && coef && qtab && info, "gx_jpeg_entropy_decode_any: null pointer");
+    return decode_entry("gx_jpeg_entropy_decode_any", data, len, coef, coef_capacity, qtab, info, kGxImageMaxDim, true);
 }
 
 }  // extern "C"

@@ -1382,6 +1382,92 @@ int gx_png_inflate(const unsigned char* data, size_t len, unsigned char* dst, si
 int gx_png_unfilter(const unsigned char* filtered, unsigned char* dst_u8, unsigned char* dst_plane0, int plane_rule, int B, int H,
                     int W, int C, gx_stream_t stream);
 
+/* ---- loose image files: JPEG and PNG frames of ANY size, mixed within one batch (genesis_amd/imagefile.py; the reference's users
+ *      point torchvision's ImageFolder-style loaders at a directory, datasets/apc_config.py:144-147: Resize, CenterCrop).
+ *      Host half (no GPU, no stream), sharing the marker walk and the Huffman code of the two entry points above:
+ *      gx_jpeg_info_any / gx_jpeg_entropy_decode_any: as gx_jpeg_info / gx_jpeg_entropy_decode, with two limits moved: frames up
+ *      to 4096 x 4096 (the PNG bound), and ONE-component (greyscale) streams beside three-component ones.  info[2] is the
+ *      component count, 1 or 3; a grey frame has one plane, padded to whole 8 x 8 blocks whatever its sampling factors say
+ *      (info[3] = 0, info[5] = info[6] = 0), and qtab receives its one table three times: 192 values are always written.
+ *      Accepted: SOF0, 8-bit samples, one component, or three in one interleaved scan with luma 1x1 / 2x1 / 2x2 and chroma
+ *      1x1, 8-bit quantisation tables, any Huffman tables, DRI / RSTn, byte stuffing; APPn and COM are skipped.  GX_EDATA, with
+ *      a message that names the case, for: progressive / extended SOF, arithmetic coding, four components (CMYK / YCCK), two
+ *      components, other sampling factors (4:4:0, 4:1:1 among them), 16-bit tables, a three-component frame whose scan is not
+ *      interleaved, frames above 4096 x 4096, a code that is not in its table, a coefficient index past 63, a stream that ends
+ *      early.  No input makes them read or write out of bounds; coef is written only below coef_capacity.
+ *      Device half: every entry point takes a per-frame descriptor table of n_frames * WORDS 64-bit words twice, the way
+ *      gx_png_pack does: table_host is checked word by word before anything is launched (a bad word: GX_EINVAL, nothing
+ *      launched), table_dev is the device copy the kernels read.  Offsets count elements of the array they index.
+ *      gx_jpeg_decode_ragged: coefficients as the host half leaves them -> dst_u8, per frame a region [H, W, 3] (RGB) or
+ *      [H, W] (grey).  Descriptor (GX_JPEGR_DESC_WORDS): H, W, NCOMP (1 or 3), SAMPLING (class; 0 for grey), COEF (index of the
+ *      frame's first int16 in coef, a multiple of 8), QTAB (index of its 192 uint16 in qtab, a multiple of 8), PLANES (byte
+ *      offset of its padded uint8 planes in scratch, a multiple of 16: 64 bytes per block), DST (byte offset in dst_u8),
+ *      WG0_IDCT / WG0_PIX (its first workgroup in the two launches: the running sums of ceil(blocks / GX_JPEGR_BLOCKS_PER_WG)
+ *      and of ceil(H / GX_JPEGR_TILE_H) * ceil(W / GX_JPEGR_TILE_W)).  coef, qtab and scratch are 16-byte aligned.  Two
+ *      launches: blocks -> planes in scratch, planes -> pixels; the arithmetic is gx_jpeg_decode_f32chw's (one shared
+ *      definition), at a frame's real edge the chroma neighbour is the edge sample.  No frame-sized LDS.
+ *      gx_png_unfilter_ragged: frames as gx_png_inflate leaves them -> dst_u8 regions [H, W, C]; gx_png_unfilter's kernel, one
+ *      workgroup per frame.  Descriptor (GX_PNGR_DESC_WORDS): H, W, C (1, 3 or 4), SRC (byte offset in filtered), DST (byte
+ *      offset in dst_u8).  H and W at most 4096.
+ *      gx_u8_resample_ragged_f32chw: per frame the uint8 [HS, WS, C] region at SRC of src is resized WHOLE to H2 x W2 with
+ *      Pillow's two-pass 8-bit BILINEAR (horizontal pass first, into a uint8 intermediate) and the window of S_h x S_w pixels
+ *      at (top', left') of that resized frame is written: dst [n_frames, 3, S_h, S_w] fp32 = byte / 255.  Only the window's
+ *      rows and columns are computed: HB / HW / VB / VW are indices into `tables` (int32) of the rows of
+ *      gx_pil_bilinear_coeffs(WS, W2) from left' on (S_w rows: bounds [S_w, 2], weights [S_w, KH]) and of
+ *      gx_pil_bilinear_coeffs(HS, H2) from top' on (S_h rows), KH / KV their ksize.  C = 1 is replicated to three planes, the
+ *      alpha of C = 4 is dropped (Pillow's convert('RGB')).  A pass whose size does not change copies (Pillow's table is then
+ *      the identity).  S_h and S_w are at most 1024.  R and WG0 (rows of a band of the frame, its first workgroup) are
+ *      written into the HOST table by gx_u8_resample_ragged_plan (host only), which must run before the table is copied to
+ *      the device; the launch checks them.  Descriptor (GX_RSR_DESC_WORDS): HS, WS, C, SRC, H2, W2, HB, HW, KH, VB, VW, KV, R,
+ *      WG0. */
+#define GX_JPEGR_DESC_WORDS 10
+#define GX_JPEGR_D_H 0
+#define GX_JPEGR_D_W 1
+#define GX_JPEGR_D_NCOMP 2
+#define GX_JPEGR_D_SAMPLING 3
+#define GX_JPEGR_D_COEF 4
+#define GX_JPEGR_D_QTAB 5
+#define GX_JPEGR_D_PLANES 6
+#define GX_JPEGR_D_DST 7
+#define GX_JPEGR_D_WG0_IDCT 8
+#define GX_JPEGR_D_WG0_PIX 9
+#define GX_JPEGR_BLOCKS_PER_WG 128
+#define GX_JPEGR_TILE_H 16
+#define GX_JPEGR_TILE_W 64
+#define GX_PNGR_DESC_WORDS 5
+#define GX_PNGR_D_H 0
+#define GX_PNGR_D_W 1
+#define GX_PNGR_D_C 2
+#define GX_PNGR_D_SRC 3
+#define GX_PNGR_D_DST 4
+#define GX_RSR_DESC_WORDS 14
+#define GX_RSR_D_HS 0
+#define GX_RSR_D_WS 1
+#define GX_RSR_D_C 2
+#define GX_RSR_D_SRC 3
+#define GX_RSR_D_H2 4
+#define GX_RSR_D_W2 5
+#define GX_RSR_D_HB 6
+#define GX_RSR_D_HW 7
+#define GX_RSR_D_KH 8
+#define GX_RSR_D_VB 9
+#define GX_RSR_D_VW 10
+#define GX_RSR_D_KV 11
+#define GX_RSR_D_R 12
+#define GX_RSR_D_WG0 13
+int gx_jpeg_info_any(const unsigned char* data, size_t len, int* info);
+int gx_jpeg_entropy_decode_any(const unsigned char* data, size_t len, short* coef, size_t coef_capacity, unsigned short* qtab,
+                               int* info);
+int gx_jpeg_decode_ragged(const long long* table_host, const long long* table_dev, int n_frames, const short* coef, long long coef_values,
+                          const unsigned short* qtab, long long qtab_values, unsigned char* scratch, long long scratch_bytes,
+                          unsigned char* dst_u8, long long dst_bytes, gx_stream_t stream);
+int gx_png_unfilter_ragged(const long long* table_host, const long long* table_dev, int n_frames, const unsigned char* filtered,
+                           long long filtered_bytes, unsigned char* dst_u8, long long dst_bytes, gx_stream_t stream);
+int gx_u8_resample_ragged_plan(long long* table_host, int n_frames, int S_h, int S_w, long long* workgroups);
+int gx_u8_resample_ragged_f32chw(const long long* table_host, const long long* table_dev, int n_frames, const unsigned char* src,
+                                 long long src_bytes, const int* tables, long long tables_values, float* dst, int S_h, int S_w,
+                                 gx_stream_t stream);
+
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
  *      bucket (parameters' gradients + the err / kl tail, genesis_amd/dp.py) is summed IN PLACE over the ranks by one
