@@ -37,6 +37,18 @@
 #ifndef GX_QH_ABL
 #define GX_QH_ABL 0
 #endif
+// schedule switches of the fp16 x 3 transposed-conv kernels (q_body's B16 path, DESIGN.md finding 59; tools/abl_build.sh A/Bs them):
+// double-buffered parity planes in kq_dgh (0 never, 1 on grids of at most two workgroups per CU, 2 always), weight slices two
+// phases ahead, the same in the three-workgroup kq_dgh (three staging rounds only: 166 VGPRs, no scratch; four rounds would take 199)
+#ifndef GX_QH_DGH_DB
+#define GX_QH_DGH_DB 2
+#endif
+#ifndef GX_QH_W2
+#define GX_QH_W2 1
+#endif
+#ifndef GX_QH_W2_DGH3
+#define GX_QH_W2_DGH3 0
+#endif
 
 namespace {
 
@@ -317,7 +329,10 @@ __device__ __forceinline__ float q_amax_parts(const float* __restrict__ parts, i
 // NQ: (position, quad) slots staged per thread per input tile (2 * CHS <= NQ * 256)
 // MI: 32-channel MFMA tiles per wave along M.  2 = the workgroup's whole 64-channel tile; 1 = one half (mh) of it --
 // the last tiles of a grid that does not divide the chip are split into two half-work workgroups (q_split_tail).
-template <int MODE, int NQ, bool STATS, int MI = 2, int PF = PF_B6, bool TAP = false>
+// DB (Q_DGH in the fp16 x 3 form): two input buffers of a hi and a lo piece plane each, the next parity plane staged behind the
+// current one's MFMAs (GX_QH_DGH_DB below)
+template <int MODE> constexpr int qh_prow(int ph) { if constexpr (MODE == Q_DGH) return QCfg<Q_DGH>::prow(ph); else return 0; }
+template <int MODE, int NQ, bool STATS, int MI = 2, int PF = PF_B6, bool TAP = false, bool DB = false>
 __device__ __forceinline__ void q_body(const float* __restrict__ in, const float* __restrict__ wp,
                                        const float* __restrict__ bias, float* __restrict__ out, const QGeom& g,
                                        float* lds, const int bx, const int by, const int par_a, const int mh = 0) {
@@ -398,8 +413,22 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
         // of them + the weight buffers still leave room for two workgroups per CU
         constexpr bool TRIM = NQ == 4 && MODE != Q_C3H;
         const int plane_bytes = TRIM ? 2 * CHS * 16 : NQ * 256 * 16;       // bytes per input piece plane
+        // Q_DGH, fp16 x 3 (finding 59): TWO input buffers of a hi and a lo plane each -- parity plane p of every chunk lives in buffer
+        // p & 1, plane p + 1 is loaded at plane p's first phase and split / stored behind the MFMAs of its second one, so a plane
+        // change costs neither a second barrier nor an exposed wait + split + store.  72 KB: two workgroups per CU
+        // (-DGX_QH_DGH_DB=0: the single-buffered schedule at three workgroups per CU)
+        // weight slices TWO phases ahead (a second register set; every NPH here is even, so the set of a phase is a constant): a
+        // phase of fp16 x 3 MFMAs is ~0.4 us, shorter than an L2 round trip.  fp16 x 3 transposed-conv forward and the
+        // double-buffered data gradient (-DGX_QH_W2=0: one phase ahead; -DGX_QH_W2_DGH3=1: also the three-workgroup data gradient)
+        constexpr bool DBI = DB && MODE == Q_DGH && F16;
+        static_assert(!DB || DBI, "double-buffered planes: the fp16 x 3 data gradient only");
+        // (the forward only at three staging rounds: with the 32 early-load registers of four rounds kq_dth_kernel<4, false, PF_F3>
+        //  would spill)
+        constexpr bool W2 = GX_QH_W2 && F16 && NPH % 2 == 0 &&
+                            (((MODE == Q_DT0H || MODE == Q_DT1H) && NQ == 3) || (MODE == Q_DGH && (DBI || (GX_QH_W2_DGH3 && NQ == 3))));
         char* const ibuf = reinterpret_cast<char*>(lds);
-        char* const wbufb = ibuf + NPL * plane_bytes;
+        const int ibuf_bytes = NPL * plane_bytes;
+        char* const wbufb = ibuf + (DBI ? 2 : 1) * ibuf_bytes;
         const int quad_l = lane >> 5;
         const int a_lane_b = (quad_l * QHLay<MODE, PF>::ROWS + (lane & 31)) * 16 + mh * 512;    // + mi * 512 + piece * TAPB / NP + tap * TAPB
         int b_lane_b[2];
@@ -416,7 +445,7 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
         const int nsc = g.K / 16;
         const int w_sbase = by * nsc * (NT * TAPB);
         float xin[NQ][8];
-        f32x4 wreg[NWH];
+        f32x4 wreg[W2 ? 2 : 1][NWH];
 #define GX_QH_LOAD_IN(sc_, plane_)                                                                     \
         {                                                                                              \
             const int po_ = MODE == Q_DGH ? (((plane_) >> 1) * g.Wi + ((plane_) & 1)) * 4 : 0;         \
@@ -424,7 +453,7 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
                 _Pragma("unroll") for (int e = 0; e < 8; ++e)                                          \
                     xin[q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(in_rsrc, voff[q], ((sc_) * 16 + e) * HiWi * 4 + po_, 0)); \
         }
-#define GX_QH_STORE_IN()                                                                               \
+#define GX_QH_STORE_IN(dst_)                                                                           \
         {                                                                                              \
             _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                           \
                 q_bf16x8 ph_, pm_, pl_;                                                                \
@@ -446,7 +475,7 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
                     ph_[e] = h_; pm_[e] = m_; pl_[e] = (__bf16)(r1_ - (float)m_);                      \
                 }                                                                                      \
                 }                                                                                      \
-                char* d_ = ibuf + (tid + q * 256) * 16;                                                \
+                char* d_ = (dst_) + (tid + q * 256) * 16;                                              \
                 if (!TRIM || tid + q * 256 < 2 * CHS) {                                                \
                 *reinterpret_cast<q_bf16x8*>(d_) = ph_;                                                \
                 if (!B1) *reinterpret_cast<q_bf16x8*>(d_ + plane_bytes) = pm_;                         \
@@ -454,21 +483,22 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
                 }                                                                                      \
             }                                                                                          \
         }
-#define GX_QH_LOAD_W(sc_, ph_)                                                                         \
+#define GX_QH_LOAD_W(set_, sc_, ph_)                                                                   \
         {                                                                                              \
             const int so_ = w_sbase + ((sc_) * NT + C::tbase(ph_)) * TAPB;                             \
             _Pragma("unroll") for (int i = 0; i < NWH; ++i)                                            \
-                wreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, (tid + i * 256) * 16, so_, 0)); \
+                wreg[set_][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, (tid + i * 256) * 16, so_, 0)); \
         }
-#define GX_QH_STORE_W(dst_)                                                                            \
+#define GX_QH_STORE_W(set_, dst_)                                                                      \
         {                                                                                              \
             _Pragma("unroll") for (int i = 0; i < NWH; ++i)                                            \
-                *reinterpret_cast<f32x4*>((dst_) + (tid + i * 256) * 16) = wreg[i];                    \
+                *reinterpret_cast<f32x4*>((dst_) + (tid + i * 256) * 16) = wreg[set_][i];              \
         }
         GX_QH_LOAD_IN(0, 0)
-        GX_QH_LOAD_W(0, 0)
-        GX_QH_STORE_IN()
-        GX_QH_STORE_W(wbufb)
+        GX_QH_LOAD_W(0, 0, 0)
+        GX_QH_STORE_IN(ibuf)
+        GX_QH_STORE_W(0, wbufb)
+        if constexpr (W2) GX_QH_LOAD_W(1, 0, 1)          // phase 1's slice: stored behind phase 0's MFMAs
         // Q_C3H: the next chunk's input loads are issued at the chunk's FIRST phase (the registers are free: 32 accumulators) --
         // with two chunks per tile a load issued at the last phase has one phase of MFMAs to hide under
         // ... and, since round 6, the transposed-conv forward: its five phases (kernel rows) read ONE input tile per chunk, so the next
@@ -478,7 +508,12 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
 #ifndef GX_QH_EARLY_DTH
 #define GX_QH_EARLY_DTH 1
 #endif
-        constexpr bool EARLY_IN = MODE == Q_C3H || (GX_QH_EARLY_DTH && (MODE == Q_DT0H || MODE == Q_DT1H));
+        // (Q_C5H has the same ten-phase chunk on one tile: -DGX_QH_EARLY_C5H=1 gives it the early loads too -- no gain on the GENESIS step, finding 59)
+#ifndef GX_QH_EARLY_C5H
+#define GX_QH_EARLY_C5H 0
+#endif
+        constexpr bool EARLY_IN = MODE == Q_C3H || (GX_QH_EARLY_DTH && (MODE == Q_DT0H || MODE == Q_DT1H)) ||
+                                  (GX_QH_EARLY_C5H && MODE == Q_C5H);
         // Q_C3H: ONE weight buffer (a second barrier per phase instead): 36 + 12 KB of LDS = three workgroups per CU -- a tile
         // is short (two chunks), its loads, bf16 split, MFMAs and stores barely overlap inside one workgroup, so the third
         // workgroup is what fills the gaps
@@ -492,20 +527,34 @@ __device__ __forceinline__ void q_body(const float* __restrict__ in, const float
                 constexpr bool last_ph = (PH_) + 1 == NPH;                                                       \
                 const bool more = !last_ph || !last_chunk;                                                       \
                 const bool in_next = C::newin(PH_) && more;      /* the next phase reads another input tile */   \
+                /* W2: this phase loads the slice of phase + 2 into set PH & 1 and stores the other set (phase + 1) */ \
+                constexpr int N2 = ((PH_) + 2) % NPH;                                                            \
+                constexpr bool wrap2 = (PH_) + 2 >= NPH;                                                         \
+                constexpr int LSET = W2 ? ((PH_) & 1) : 0, SSET = W2 ? (((PH_) + 1) & 1) : 0;                     \
+                /* DBI: plane PL is read out of buffer PL & 1; at its first phase (row 0) the next plane is loaded, at its second   \
+                   (row 1: the middle one of three or the last of two) split and stored into the other buffer, which everyone     \
+                   left at the barrier of row 0 */                                                               \
+                constexpr int PL = C::plane(PH_), PROW = qh_prow<MODE>(PH_);                                     \
+                const bool pl_next = DBI && (PL < 3 || !last_chunk);                                             \
                 __syncthreads();                                                                                 \
-                if (more) GX_QH_LOAD_W(last_ph ? sc + 1 : sc, NXT)                                               \
-                if (EARLY_IN) { if ((PH_) == 0 && !last_chunk && !(GX_QH_ABL & 8)) GX_QH_LOAD_IN(sc + 1, 0) }    \
+                if constexpr (W2) { if (!wrap2 || !last_chunk) GX_QH_LOAD_W(LSET, wrap2 ? sc + 1 : sc, N2) }     \
+                else if (more) GX_QH_LOAD_W(0, last_ph ? sc + 1 : sc, NXT)                                       \
+                if (DBI) { if (PROW == 0 && pl_next && !(GX_QH_ABL & 8)) GX_QH_LOAD_IN(PL == 3 ? sc + 1 : sc, (PL + 1) & 3) } \
+                else if (EARLY_IN) { if ((PH_) == 0 && !last_chunk && !(GX_QH_ABL & 8)) GX_QH_LOAD_IN(sc + 1, 0) } \
                 else if (in_next) GX_QH_LOAD_IN(last_ph ? sc + 1 : sc, C::plane(NXT))                            \
-                q_phase_h<MODE, (PH_), NCLS, MI, PF>(acc, ibuf, wbufb + (ONE_W ? 0 : (s & 1)) * WSLOTB, plane_bytes, \
+                q_phase_h<MODE, (PH_), NCLS, MI, PF>(acc, ibuf + (DBI ? (PL & 1) * ibuf_bytes : 0),              \
+                                                 wbufb + (ONE_W ? 0 : (s & 1)) * WSLOTB, plane_bytes,            \
                                                  a_lane_b, b_lane_b[0], b_lane_b[1], HS16);                      \
                 if (ONE_W) {                      /* one weight buffer: everyone is done with it (and the tile) */ \
-                    if (more) { __syncthreads(); GX_QH_STORE_W(wbufb) }                                          \
-                    if (in_next && !(GX_QH_ABL & 2)) GX_QH_STORE_IN()                                            \
+                    if (more) { __syncthreads(); GX_QH_STORE_W(0, wbufb) }                                       \
+                    if (in_next && !(GX_QH_ABL & 2)) GX_QH_STORE_IN(ibuf)                                        \
                 } else {                                                                                         \
-                if (more) GX_QH_STORE_W(wbufb + ((s + 1) & 1) * WSLOTB)                                          \
-                if (in_next) {                    /* the input tile is single-buffered: everyone is done with it */ \
+                if (more) GX_QH_STORE_W(SSET, wbufb + ((s + 1) & 1) * WSLOTB)                                    \
+                if (DBI) {                                                                                       \
+                    if (PROW == 1 && pl_next && !(GX_QH_ABL & 2)) GX_QH_STORE_IN(ibuf + ((PL + 1) & 1) * ibuf_bytes) \
+                } else if (in_next) {             /* the input tile is single-buffered: everyone is done with it */ \
                     __syncthreads();                                                                             \
-                    if (!(GX_QH_ABL & 2)) GX_QH_STORE_IN()                                                       \
+                    if (!(GX_QH_ABL & 2)) GX_QH_STORE_IN(ibuf)                                                   \
                 }                                                                                                \
                 }                                                                                                \
                 ++s;                                                                                             \
@@ -905,14 +954,15 @@ kq_dt_kernel(const float* __restrict__ in, const float* __restrict__ wp0, const 
     }
 }
 
-template <int NQ, int PF = PF_B6>
+// DB: the double-buffered plane pairs of the fp16 x 3 form (q_body), two workgroups per CU by its LDS
+template <int NQ, int PF = PF_B6, bool DB = false>
 __global__ void __launch_bounds__(256, 2)
 kq_dgh_kernel(const float* __restrict__ in, const float* __restrict__ wp, float* __restrict__ out, QGeom g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // (XCD-aware tile map over the whole-tile workgroups: neighbouring tiles, which share halo rows, on one XCD's L2)
     const int bx = (int)blockIdx.x < g.nfull ? gx_xcd_tile(blockIdx.x, g.nfull) : (int)blockIdx.x;
-    if (bx < g.nfull) q_body<Q_DGH, NQ, false, 2, PF>(in, wp, nullptr, out, g, lds, bx, blockIdx.y, 0);
-    else q_body<Q_DGH, NQ, false, 1, PF>(in, wp, nullptr, out, g, lds, g.nfull + ((bx - g.nfull) >> 1), blockIdx.y, 0, (bx - g.nfull) & 1);
+    if (bx < g.nfull) q_body<Q_DGH, NQ, false, 2, PF, false, DB>(in, wp, nullptr, out, g, lds, bx, blockIdx.y, 0);
+    else q_body<Q_DGH, NQ, false, 1, PF, false, DB>(in, wp, nullptr, out, g, lds, g.nfull + ((bx - g.nfull) >> 1), blockIdx.y, 0, (bx - g.nfull) & 1);
 }
 
 // conv3x3 on the bf16 pipe, 32 output channels per workgroup (blockIdx.y)
@@ -1216,10 +1266,11 @@ static int kq_fold_parts(const float** parts, int* n, float* amax_ws, hipStream_
 // (np < 3: the launch's allocation in the fp16 x 3 form -- two planes, two-piece weight taps: 48 KB at three staging rounds, i.e. THREE
 //  workgroups per CU where the registers allow it (kq_dgh_kernel<3, PF_F3>: 156) -- or the one-piece form (one plane, one-piece taps);
 //  eligibility is always decided on the three-piece size: every form covers the same layers)
-static size_t qh_lds(const QGeom& g, int nq, int np = 3) {
+// (nbuf = 2: the double-buffered plane pairs of kq_dgh_kernel<.., PF_F3, true> -- 72 KB at three staging rounds, two workgroups per CU)
+static size_t qh_lds(const QGeom& g, int nq, int np = 3, int nbuf = 1) {
     const int NWH = (3 * (np * 2048 / 16) + 255) / 256;
     const int CHS = (1 << g.lG) * ((1 << g.lTH) + 2) * ((1 << g.lTW) + 2);
-    const size_t planes = nq == 4 ? (size_t)np * 2 * CHS * 16 : (size_t)np * nq * 256 * 16;
+    const size_t planes = (size_t)nbuf * (nq == 4 ? (size_t)np * 2 * CHS * 16 : (size_t)np * nq * 256 * 16);
     const size_t lds = planes + (size_t)2 * NWH * 256 * 16;
     return lds <= 80 * 1024 ? lds : 0;
 }
@@ -1446,6 +1497,17 @@ int gx_kq_deconv_dgrad_h_launch(const float* dy, const float* wp, float* dx, int
             g.x_amax = x_parts ? x_parts : amax_ws;
             if (x_parts) g.x_amax_n = x_nparts;
             g.w_amax = w_amax;
+#if GX_QH_DGH_DB
+            // double-buffered plane pairs where they leave room for two workgroups per CU (every three-round tile; four-round
+            // tiles of at most 448 halo positions: the 6 x 66 of a 64 x 64 base grid are 396); GX_QH_DGH_DB == 1: only where the
+            // grid has at most two workgroups per CU anyway (a larger grid runs three of the single-buffered ones per CU) -- on
+            // the metric step the second buffer hides more than the third workgroup does, so the default is every grid (finding 59)
+            static bool d3 = false, d4 = false;
+            const size_t lds_db = GX_QH_DGH_DB >= 2 || (size_t)grid.x * grid.y <= 2 * 256 ? qh_lds(g, nq, 2, 2) : 0;
+            if (lds_db > 0 && nq == 3) { q_set_attr(&kq_dgh_kernel<3, PF_F3, true>, &d3); hipLaunchKernelGGL((kq_dgh_kernel<3, PF_F3, true>), grid, dim3(256), lds_db, s, dy, wp, dx, g); }
+            else if (lds_db > 0) { q_set_attr(&kq_dgh_kernel<4, PF_F3, true>, &d4); hipLaunchKernelGGL((kq_dgh_kernel<4, PF_F3, true>), grid, dim3(256), lds_db, s, dy, wp, dx, g); }
+            else
+#endif
             if (nq == 3) { q_set_attr(&kq_dgh_kernel<3, true>, &f3); hipLaunchKernelGGL((kq_dgh_kernel<3, true>), grid, dim3(256), lds, s, dy, wp, dx, g); }
             else { q_set_attr(&kq_dgh_kernel<4, true>, &f4); hipLaunchKernelGGL((kq_dgh_kernel<4, true>), grid, dim3(256), lds, s, dy, wp, dx, g); }
         } else
