@@ -1055,6 +1055,21 @@ gn_relu_bwd_small_kernel(const float* __restrict__ y, const float* __restrict__ 
     }
 }
 
+// gx_gn_last_plan: the record of this thread's last gn_relu_fwd_impl / gn_relu_bwd_impl launch.  Every launcher below fills it
+// on the host, just before it launches, from the values that launch uses (template arguments, grid, block, dynamic LDS, the
+// views' slab counts); nothing reads it on the launch path.  Field order = the GX_GN_PLAN_* indices of include/genesis_hip.h.
+struct GxGnPlan { int kernel, vec, F, UPW, P, threads, grid, lds, CT, keep, wp, chunks, ns0, ns1, ns_in; };
+static_assert(sizeof(GxGnPlan) == GX_GN_PLAN_FIELDS * sizeof(int), "GxGnPlan and GX_GN_PLAN_FIELDS disagree");
+thread_local GxGnPlan t_gn_plan = {};       // kernel GX_GN_NONE until this thread's first launch
+inline void gn_plan_note_fwd(int kernel, bool vec, int F, int UPW, int P, dim3 grid, dim3 block, const InSrc& src) {
+    t_gn_plan = GxGnPlan{kernel, vec ? 1 : 0, F, UPW, P, (int)block.x, (int)grid.x, 0, 0, 0, 0, 0, 0, 0, src.nsplit};
+}
+inline void gn_plan_note_bwd(int kernel, bool vec, int F, int UPW, int P, dim3 grid, dim3 block, size_t lds, int CT, bool keep,
+                             const float* wpart, int chunks, const View& g0, const View& g1) {
+    t_gn_plan = GxGnPlan{kernel, vec ? 1 : 0, F, UPW, P, (int)block.x, (int)grid.x, (int)lds, CT, keep ? 1 : 0, wpart ? 1 : 0,
+                         chunks, g0.nsplit, g1.ptr ? g1.nsplit : 0, 0};
+}
+
 // threads for the tiny-slab kernels, or 0 if the shape does not qualify
 int small_threads(int cpg, int H, int W) {
     const int HW = H * W, m = cpg * HW;
@@ -1073,6 +1088,7 @@ template <int F, int UPW>
 void launch_fwd_reg(dim3 grid, dim3 block, hipStream_t s, const InSrc src, const float* gamma, const float* beta, int C, int H,
                     int W, int groups, int P, float eps, View d0, View d1, float* mean, float* rstd) {
     float* ap = d0.ptr ? gn_take_link_out(d0.ptr, d0.ctot, d0.c0, d0.mode, C, grid.x, (size_t)(grid.x / groups) * C * H * W, d1.ptr != nullptr) : nullptr;
+    gn_plan_note_fwd(GX_GN_FWD_REG, true, F, UPW, P, grid, block, src);
     hipLaunchKernelGGL((gn_relu_fwd_reg_kernel<F, UPW>), grid, block, 0, s, src, gamma, beta, C, H, W, groups, P, eps, d0, d1,
                        mean, rstd, ap);
 }
@@ -1097,9 +1113,10 @@ bool launch_bwd_stage(dim3 grid, dim3 block, hipStream_t s, size_t lds, const fl
 #define GX_STAGE_LAUNCH(WP_)                                                                                               \
     hipLaunchKernelGGL((gn_relu_bwd_stage_kernel<F, 4, WP_, KEEP>), grid, block, lds, s, y, gamma, beta, mean, rstd, C, H, W, \
                        groups, P, g0, g1, dy, part, wpart, bpart, amax_parts)
+    gn_plan_note_bwd(GX_GN_BWD_STAGE, true, F, UPW, P, grid, block, lds, 4, KEEP, wpart, 0, g0, g1);
     if (wpart) GX_STAGE_LAUNCH(true); else GX_STAGE_LAUNCH(false);
 #undef GX_STAGE_LAUNCH
-    return true;
+    return true;        // (the record was written above, before the launch)
 }
 
 template <int F, int UPW>
@@ -1108,6 +1125,7 @@ void launch_bwd_reg(dim3 grid, dim3 block, hipStream_t s, size_t lds, const floa
                     float* part, float* wpart, float* bpart) {
     if (!lds) {
         float* ap = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)(grid.x / groups) * C * H * W);      // (an armed amax link: dy's partial maxima for its consumer)
+        gn_plan_note_bwd(GX_GN_BWD_REG, true, F, UPW, P, grid, block, 0, 0, false, wpart, 0, g0, g1);
         hipLaunchKernelGGL((gn_relu_bwd_reg_kernel<F, UPW, false>), grid, block, 0, s, y, gamma, beta, mean, rstd, C, H, W, groups,
                            P, g0, g1, dy, part, wpart, bpart, ap);
         return;
@@ -1121,6 +1139,7 @@ void launch_bwd_reg(dim3 grid, dim3 block, hipStream_t s, size_t lds, const floa
     if (launch_bwd_stage<F, UPW>(grid, block, s, lds, y, gamma, beta, mean, rstd, C, H, W, groups, P, g0, g1, dy, part, wpart, bpart))
         return;
     float* ap = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)(grid.x / groups) * C * H * W);
+    gn_plan_note_bwd(GX_GN_BWD_REG_STAGED, true, F, UPW, P, grid, block, lds, 0, false, wpart, 0, g0, g1);
     hipLaunchKernelGGL((gn_relu_bwd_reg_kernel<F, UPW, true>), grid, block, lds, s, y, gamma, beta, mean, rstd, C, H, W, groups, P,
                        g0, g1, dy, part, wpart, bpart, ap);
 }
@@ -1432,6 +1451,12 @@ int gx_defer_flush_gn(const GxGnRed* items, int n, hipStream_t s) {
 
 extern "C" {
 
+int gx_gn_last_plan(int* out, int n) {
+    const int* f = reinterpret_cast<const int*>(&t_gn_plan);
+    for (int i = 0; out && i < n && i < GX_GN_PLAN_FIELDS; ++i) out[i] = f[i];
+    return GX_GN_PLAN_FIELDS;
+}
+
 static int gn_relu_fwd_impl(const InSrc& src, const float* gamma, const float* beta, int N, int C, int H, int W,
                             int groups, float eps, float* dst0, int dst0_ctot, int dst0_c0, int dst0_mode,
                             float* dst1, int dst1_ctot, int dst1_c0, int dst1_mode, float* mean, float* rstd,
@@ -1485,13 +1510,15 @@ static int gn_relu_fwd_impl(const InSrc& src, const float* gamma, const float* b
         if (pl.ok)
             GX_GN_REG_DISPATCH(launch_fwd_reg, pl, dim3(N * groups), dim3(pl.threads), (hipStream_t)stream, src, gamma,
                                beta, C, H, W, groups, pl.P, eps, d0, d1, mean, rstd);
-        else if (st)
+        else if (st) {
+            gn_plan_note_fwd(GX_GN_FWD_SMALL, true, 0, 0, 0, dim3(N * groups), dim3(st), src);
             hipLaunchKernelGGL(gn_relu_fwd_small_kernel, dim3(N * groups), dim3(st), 0, (hipStream_t)stream, src, gamma,
                                beta, C, H, W, groups, eps, d0, d1, mean, rstd);
-        else {
+        } else {
             // (an armed amax tap and the link are served by the generic kernels too -- the 128 x 128 model's decoder: K B x 8 = 2816
             //  partial maxima, which every workgroup of the conv that reads them reduces with 16-byte loads)
             float* ap = dst0 ? gn_take_link_out(dst0, d0.ctot, d0.c0, d0.mode, C, (unsigned)(N * groups), (size_t)N * C * H * W, dst1 != nullptr) : nullptr;
+            gn_plan_note_fwd(GX_GN_FWD_TWOPASS, vec, 0, 0, 0, dim3(N * groups), dim3(threads), src);
             if (vec)
                 hipLaunchKernelGGL(gn_relu_fwd_kernel<true>, dim3(N * groups), dim3(threads), 0, (hipStream_t)stream, src,
                                    gamma, beta, C, H, W, groups, eps, d0, d1, mean, rstd, ap);
@@ -1591,21 +1618,23 @@ static int gn_relu_bwd_impl(const float* y, const float* gamma, const float* bet
             const int chunks = hw / kSplitPix;
             float* rec = (float*)ws + (size_t)N * C * 3;
             float* kk = rec + (size_t)N * groups * chunks * kSplitRec;
-            const dim3 grid(N * groups * chunks);
-            if (v0.ctot <= 4)
-                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<4>, grid, dim3(256), 0, s, y, gamma, beta, mean, rstd, C, hw,
+            const dim3 grid(N * groups * chunks), block(256);
+            const int CT = v0.ctot <= 4 ? 4 : 8;      // the template's output-channel count (rows beyond v0.ctot are idle)
+            gn_plan_note_bwd(GX_GN_BWD_SPLIT, true, 0, 0, 0, grid, block, 0, CT, false, wpart, chunks, v0, v1);
+            if (CT == 4)
+                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<4>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
                                    groups, v0, rec);
             else
-                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<8>, grid, dim3(256), 0, s, y, gamma, beta, mean, rstd, C, hw,
+                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<8>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
                                    groups, v0, rec);
             hipLaunchKernelGGL(gn_bwd_proj_split_combine_kernel, dim3(N * groups), dim3(64), 0, s, (const float*)rec, gamma, rstd,
                                C, hw, groups, chunks, v0.ctot, kk, (float*)ws, wpart, bpart);
             float* ap = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)N * C * H * W);      // (dy: a whole plain tensor)
-            if (v0.ctot <= 4)
-                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<4>, grid, dim3(256), 0, s, y, gamma, beta, mean, rstd, C, hw,
+            if (CT == 4)
+                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<4>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
                                    groups, v0, (const float*)kk, dy, ap);
             else
-                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<8>, grid, dim3(256), 0, s, y, gamma, beta, mean, rstd, C, hw,
+                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<8>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
                                    groups, v0, (const float*)kk, dy, ap);
         }
         else if (pl.ok) {
@@ -1617,11 +1646,13 @@ static int gn_relu_bwd_impl(const float* y, const float* gamma, const float* bet
         }
         else if (wpart)
             GX_CHECK_ARG(false, "gx_gn_relu_bwd_proj: fused 1x1 weight gradient unsupported for this shape");
-        else if (st)
+        else if (st) {
+            gn_plan_note_bwd(GX_GN_BWD_SMALL, true, 0, 0, 0, dim3(N * groups), dim3(st), 0, 0, false, nullptr, 0, v0, v1);
             hipLaunchKernelGGL(gn_relu_bwd_small_kernel, dim3(N * groups), dim3(st), 0, s, y, gamma, beta, mean, rstd,
                                C, H, W, groups, v0, v1, dy, (float*)ws);
-        else {
+        } else {
             float* ap = gx_amax_producer_out(dy, false, (unsigned)(N * groups), (size_t)N * C * H * W);
+            gn_plan_note_bwd(GX_GN_BWD_TWOPASS, vec, 0, 0, 0, dim3(N * groups), dim3(threads), 0, 0, false, nullptr, 0, v0, v1);
             if (vec)
                 hipLaunchKernelGGL(gn_relu_bwd_kernel<true>, dim3(N * groups), dim3(threads), 0, s, y, gamma, beta, mean,
                                    rstd, C, H, W, groups, v0, v1, dy, (float*)ws, ap);

@@ -303,6 +303,24 @@ def conv_last_plan():
     return plan
 
 
+# ------------------------------------------------------------------ the kernel of the last GroupNorm launch (gx_gn_last_plan)
+GN_PLAN_FIELDS = ('kernel', 'vec', 'F', 'UPW', 'P', 'threads', 'grid', 'lds', 'CT', 'KEEP', 'WP', 'chunks', 'nsplit0', 'nsplit1',
+                  'nsplit_in')                                                    # the GX_GN_PLAN_* indices of include/genesis_hip.h
+GN_PLAN_KERNELS = ('none', 'fwd_reg', 'fwd_small', 'fwd_twopass', 'bwd_reg', 'bwd_reg_staged', 'bwd_stage', 'bwd_small',
+                   'bwd_twopass', 'bwd_split')                                    # GX_GN_NONE ... GX_GN_BWD_SPLIT
+
+
+def gn_last_plan():
+    """The kernel and launch geometry of this thread's last GroupNorm + ReLU forward / backward launch as a dict (kernel by
+    name, the rest integers; kernel 'none' before any launch).  Host state only: needs no GPU and does not synchronise."""
+    buf = (ctypes.c_int * len(GN_PLAN_FIELDS))()
+    n = int(_lib.load().gx_gn_last_plan(buf, len(GN_PLAN_FIELDS)))
+    assert n == len(GN_PLAN_FIELDS), 'gx_gn_last_plan has %d fields, hip_ops.GN_PLAN_FIELDS %d' % (n, len(GN_PLAN_FIELDS))
+    plan = dict(zip(GN_PLAN_FIELDS, (int(v) for v in buf)))
+    plan['kernel'] = GN_PLAN_KERNELS[plan['kernel']]
+    return plan
+
+
 # ------------------------------------------------------------------ conv3x3
 def conv3x3_fwd(x, w, amax_in=None):
     _chk(x, 'conv3x3_fwd.x'); _chk(w, 'conv3x3_fwd.w')

@@ -321,6 +321,41 @@ int gx_gn_relu_active_count(const float* y, const float* gamma, const float* bet
 /*      workspace of gx_gn_relu_bwd_proj (>= gx_gn_relu_bwd_ws_bytes): slabs too large for one workgroup (128 x 128 images) are
  *      processed in 4096-pixel chunks -- chunk sums, per-slab constants, chunked apply -- whose records live here */
 size_t gx_gn_relu_bwd_proj_ws_bytes(int N, int C, int H, int W, int groups, int Cout);
+/*      gx_gn_last_plan(out, n): the kernel and launch geometry of this thread's most recent gx_gn_relu_fwd* / gx_gn_relu_bwd* launch,
+ *      written by the launcher on the host just before it launches, every field copied from the values the launch itself uses.
+ *      Fills out[0 .. min(n, GX_GN_PLAN_FIELDS)) in the order of the GX_GN_PLAN_* indices below and returns GX_GN_PLAN_FIELDS;
+ *      before any such launch the kernel is GX_GN_NONE and every other field 0.  A field the kernel does not have is 0.  The
+ *      parameter-gradient reduce that ends a backward call leaves the record alone, and so does a call that is refused.  For
+ *      tests and diagnosis: no synchronisation, no device work. */
+#define GX_GN_PLAN_FIELDS 15
+/*      out[] indices */
+#define GX_GN_PLAN_KERNEL 0       /* GX_GN_NONE ... GX_GN_BWD_SPLIT */
+#define GX_GN_PLAN_VEC 1          /* 1: 16-byte accesses along W; 0: the scalar two-pass kernels (W == 2) */
+#define GX_GN_PLAN_F 2            /* register kernels: float4 per lane and unit, units per wave, parts per channel */
+#define GX_GN_PLAN_UPW 3
+#define GX_GN_PLAN_P 4
+#define GX_GN_PLAN_THREADS 5      /* workgroup size */
+#define GX_GN_PLAN_GRID 6         /* workgroups (the chunked path: of its sums and apply launches) */
+#define GX_GN_PLAN_LDS 7          /* dynamic LDS bytes (the staged output gradient of the following 1x1 conv) */
+#define GX_GN_PLAN_CT 8           /* the template's 1x1-conv output channels: 4 (stage kernel), 4 / 8 (chunked path) */
+#define GX_GN_PLAN_KEEP 9         /* stage kernel: y stays in registers between the passes */
+#define GX_GN_PLAN_WP 10          /* the launch also writes wpart / bpart */
+#define GX_GN_PLAN_CHUNKS 11      /* chunked path: 4096-pixel chunks per slab */
+#define GX_GN_PLAN_NSPLIT0 12     /* backward: split-K slabs of gradient source 0 and source 1 (0: no such source, or mode 3) */
+#define GX_GN_PLAN_NSPLIT1 13
+#define GX_GN_PLAN_NSPLIT_IN 14   /* forward: split-K slabs of the input */
+/*      kernels */
+#define GX_GN_NONE 0
+#define GX_GN_FWD_REG 1           /* gn_relu_fwd_reg_kernel<F, UPW> */
+#define GX_GN_FWD_SMALL 2         /* gn_relu_fwd_small_kernel */
+#define GX_GN_FWD_TWOPASS 3       /* gn_relu_fwd_kernel<VEC> */
+#define GX_GN_BWD_REG 4           /* gn_relu_bwd_reg_kernel<F, UPW, false> */
+#define GX_GN_BWD_REG_STAGED 5    /* gn_relu_bwd_reg_kernel<F, UPW, true> */
+#define GX_GN_BWD_STAGE 6         /* gn_relu_bwd_stage_kernel<F, 4, WP, KEEP> */
+#define GX_GN_BWD_SMALL 7         /* gn_relu_bwd_small_kernel */
+#define GX_GN_BWD_TWOPASS 8       /* gn_relu_bwd_kernel<VEC> */
+#define GX_GN_BWD_SPLIT 9         /* gn_bwd_proj_split_sums_kernel<CT> / _combine_kernel / _apply_kernel<CT> */
+int gx_gn_last_plan(int* out, int n);
 
 /* ---- Instance-Colouring stick-breaking attention: modules/attention.py:162-226.
  *      colour [B,C<=8,H,W]; log_sigma: device pointer to the fp64 0-dim parameter; rand_pixel [B,1,H,W];
