@@ -4,7 +4,11 @@
 Every segmentation score of a batch comes from one gx_seg_metrics launch (genesis_amd.metrics.SegMetrics: the K log-mask planes
 read in place, no cat / argmax / label-map round trip), the loss statistics are accumulated on the device in the reference's
 operation order, and each function brings its results to the host in ONE transfer at the end.  The only other host reads are the
-ones inside the loader and the model (dynamic_K's, for instance)."""
+ones inside the loader and the model (dynamic_K's, for instance).
+
+Not in the reference: reconstruction quality for data without labels -- `evaluation(..., image_quality=True)` and
+`reconstruction_quality_from_model` (per-image MSE, RMSE, PSNR, SSIM from one gx_image_quality launch per batch:
+genesis_amd.image_quality.ImageQuality), in the same single transfer."""
 import datetime
 import itertools
 import time
@@ -13,6 +17,7 @@ import numpy as np
 import torch
 
 from . import compat
+from .image_quality import KEYS as _QUALITY_KEYS, ImageQuality
 from .metrics import SegMetrics
 
 compat.install()
@@ -87,7 +92,8 @@ class _MaskScores:
         return {field: m._finish(host[12 * i:12 * (i + 1)]) for i, (field, m) in enumerate(self.metrics.items())}
 
 
-def evaluation(model, data_loader, writer, config, iter_idx, N_eval=None, N_seg_metrics=50, max_labels=32):
+def evaluation(model, data_loader, writer, config, iter_idx, N_eval=None, N_seg_metrics=50, max_labels=32, image_quality=False,
+               data_range=1.0):
     """train.py:479-589: the statistics of a validation run as a dict of Python floats, logged as 'val/<key>' when `writer` is
     given.  Kept from the reference: the num_batches rule (5 batches at iter_idx == 0 or under config.debug, N_eval // batch_size
     when N_eval fits the loader, else all); per loss key the mean over batches of the batch means (lists of K terms summed over
@@ -98,16 +104,21 @@ def evaluation(model, data_loader, writer, config, iter_idx, N_eval=None, N_seg_
     than needed is drawn from the loader; host batches are moved with .cuda() in place under config.gpu; the printed lines.
     The model ends in train mode, also when the loop raises; the grad mode is put back to what it was on entry (the reference
     leaves it enabled: the same thing for its caller).  Host mask planes are moved to the device by SegMetrics.
-    max_labels: bound on the ground-truth labels (genesis_amd.metrics.SegMetrics)."""
+    max_labels: bound on the ground-truth labels (genesis_amd.metrics.SegMetrics).
+    image_quality=True (not in the reference): every evaluated batch's reconstruction -- the forward's first output -- and
+    batch['input'] go through one genesis_amd.image_quality.ImageQuality.update (data range `data_range`, the default window), and
+    the result gains 'mse', 'rmse', 'psnr', 'ssim', each the mean over the images, after 'err_element'; they ride in the same
+    transfer.  With the default nothing is launched or returned that was not before."""
     model.eval()
     try:
         with torch.no_grad():
-            return _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metrics, max_labels)
+            return _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metrics, max_labels,
+                               ImageQuality(data_range=data_range) if image_quality else None)
     finally:
         model.train()
 
 
-def _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metrics, max_labels):
+def _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metrics, max_labels, quality=None):
     batch_size = data_loader.batch_size
     num_batches, line, flush = _batch_budget(data_loader, iter_idx, config.debug, N_eval)
     fprint(line, flush)
@@ -126,8 +137,10 @@ def _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metr
     for b_idx, batch in enumerate(itertools.islice(batches, num_batches)):
         if config.gpu:
             batch.update({key: val.cuda() for key, val in batch.items()})
-        _, losses, stats, _, _ = model(batch['input'])
+        recon, losses, stats, _, _ = model(batch['input'])
         shape = batch['input'].shape
+        if quality is not None:
+            quality.update(recon, batch['input'])
         means = {key: _batch_mean(val) for key, val in losses.items()}
         for key, v in means.items():
             add(key, v)
@@ -147,7 +160,8 @@ def _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metr
     loss_keys = [key for key, entry in totals.items() if entry is not None]
     values = [totals[key][0] / totals[key][1] for key in loss_keys]
     values.append(values[loss_keys.index('err')] / int(np.prod(shape[1:4])))
-    host = _fetch(values + scores.parts())
+    seg_parts = scores.parts()
+    host = _fetch(values + seg_parts + (quality._parts() if quality is not None else []))
     loss_host, seg_host = dict(zip(loss_keys + ['err_element'], host)), scores.finish(host[len(values):])
 
     checked = iter_idx > 0 and not config.debug
@@ -161,6 +175,9 @@ def _evaluation(model, data_loader, writer, config, iter_idx, N_eval, N_seg_metr
             assert N_seg_metrics <= scores.updates[field] * batch_size < N_seg_metrics + batch_size
         result[key] = seg_host[field][key[:len(key) - len(suffix)]]
     result['err_element'] = float(loss_host['err_element'])
+    if quality is not None:
+        quality_host = quality._finish(host[len(values) + sum(t.numel() for t in seg_parts):])
+        result.update({key: quality_host[key] for key in _QUALITY_KEYS})
     duration = time.time() - started
     fprint(f'Eval duration: {duration:.1f}s, {num_batches / duration:.1f} b/s')
     result.update(duration=float(duration), num_batches=float(num_batches))
@@ -239,3 +256,17 @@ def seg_metrics_from_model(model, batches, max_labels=32):
         fprint(f"Average {tag} ARI: {out['ari_fg' + suffix]}")
         fprint(f"Average {tag} MSC: {torch.tensor(out['msc_fg' + suffix], dtype=torch.float32)}")
     return out
+
+
+def reconstruction_quality_from_model(model, batches, data_range=1.0, win_size=11, sigma=1.5, keep_per_image=0):
+    """MSE, RMSE, PSNR and SSIM of the model's reconstructions of prefetched `batches` ({'input'}, any batch sizes), the sibling of
+    seg_metrics_from_model for data without labels: eval mode, no gradients, one ImageQuality.update per batch and one transfer at
+    the end.  Returns ImageQuality.compute()'s dict (means over the images, 'num_images', 'num_batches', and 'per_image' with
+    keep_per_image > 0).  The model is left in eval mode."""
+    model.eval()
+    quality = ImageQuality(data_range=data_range, win_size=win_size, sigma=sigma, keep_per_image=keep_per_image)
+    with torch.no_grad():
+        for x in batches:
+            inp = x['input'].cuda() if _on_device(model) else x['input']
+            quality.update(model(inp)[0], inp)
+    return quality._finish(_fetch(quality._parts()))

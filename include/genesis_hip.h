@@ -1036,6 +1036,35 @@ int gx_seg_metrics(const float* base, long long plane_stride, long long image_st
                    const long long* instances, int B, int HW, int K, int max_labels, double* rows, double* acc,
                    unsigned long long* state, double* log, long long log_capacity, gx_stream_t stream);
 
+/* ---- reconstruction quality on the device (genesis_amd/image_quality.py): per image b of pred / target (fp32 [B, C, H, W], image b
+ *      at base + b image_stride floats, each image C H W contiguous floats) the row rows[b] = (mse, rmse, psnr, ssim) in fp64 --
+ *      every operation from the load onwards is fp64, each rounded on its own (no contraction):
+ *        mse  = (1 / (C H W)) sum (pred - target)^2 (train.py:244 in fp64),  rmse = sqrt(mse),
+ *        psnr = 10 log10(data_range^2 / mse), +inf when mse == 0; NaN inputs give NaN,
+ *        ssim = mean over channels and VALID window positions ((H - win + 1) x (W - win + 1), no padding) of
+ *               ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sx2 + sy2 + C2)),  C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2,
+ *               mx = g * x, my = g * y, sx2 = g * x^2 - mx^2, sy2 = g * y^2 - my^2, sxy = g * (x y) - mx my, g the outer product of
+ *               `window` (a HOST array of `win` fp64 taps that sum to 1: genesis_amd.image_quality.gaussian_window) with itself.
+ *      ONE launch.  Tile plan: a workgroup owns one 16 x 16 tile of valid positions of one image and loops over the channels; it
+ *      stages the haloed (16 + win - 1)^2 patch of both tensors in LDS once per channel, runs the window as a row pass then a column
+ *      pass over the five maps, and adds its tile's SSIM values and squared errors in a fixed order into the tile's slot of ws.
+ *      Squared error: every pixel exactly once -- a tile owns the 16 x 16 pixels at its valid positions, and the last tile of a row
+ *      (column) of tiles also owns the win - 1 trailing columns (rows), which lie inside its staged patch.  No floating-point
+ *      atomics: the last workgroup to arrive (state[0], an integer counter that it puts back to 0) adds every image's slots in tile
+ *      order, writes the rows, adds them to acc[0..4) in image order, adds B to state[1] and 1 to state[2], copies the rows to
+ *      log[state[3] ..] while they fit into log_capacity rows (log may be NULL) and advances state[3].  An image's row is the same
+ *      bits whatever batch it arrives in.  16-byte loads when W % 4 == 0, both bases are 16-byte aligned and both image strides are
+ *      multiples of 4; 4-byte loads otherwise.  GX_EINVAL before any launch: a null pred, target, window, rows, acc, state or ws;
+ *      win even or outside [3, 11]; B or C < 1; H or W below win or above 4096; data_range not positive and finite; an image
+ *      stride below C H W; ws_bytes below gx_image_quality_ws_bytes (two doubles per tile; 0 for a shape that is refused).
+ *      rows fp64 [B, 4] (scratch); acc fp64 [4] and state [4] = (arrival counter, images, batches, log cursor) zero before the
+ *      first launch; launches on one stream may share them and ws. */
+int gx_image_quality(const float* pred, long long pred_image_stride, const float* target, long long target_image_stride, int B,
+                     int C, int H, int W, const double* window, int win, double data_range, double* rows, double* acc,
+                     unsigned long long* state, double* log, long long log_capacity, void* ws, size_t ws_bytes,
+                     gx_stream_t stream);
+size_t gx_image_quality_ws_bytes(int B, int C, int H, int W, int win);
+
 /* ---- TensorBoard image grids on the device (train.py:423-476 visualise_outputs, utils/misc.py:82-98 colour_seg_masks,
  *      torchvision.utils.make_grid; genesis_amd/visualise.py).  gx_vis_compose: ONE launch fills a whole atlas -- `atlas`, a flat
  *      device buffer of atlas_words 4-byte words holding any number of grids back to back, its LAST word an unsigned overflow
