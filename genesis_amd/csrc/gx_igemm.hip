@@ -250,6 +250,8 @@ int ig_geom(const char* name, IG* g, int mode, int N, int Cin, int Cout, int H, 
     GX_CHECK_ARG(N > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, "%s: bad dims", name);
     GX_CHECK_ARG(k >= 1 && k <= 5 && stride >= 1 && pad >= 0, "%s: kernel <= 5x5, stride >= 1", name);
     g->N = N; g->Cin = Cin; g->Cout = Cout; g->H = H; g->W = W; g->k = k; g->stride = stride; g->pad = pad;
+    // (a window larger than the padded input: the division below truncates -1 / 2 to 0 and would answer one output row)
+    GX_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k, "%s: empty output", name);
     g->Ho = (H + 2 * pad - k) / stride + 1;
     g->Wo = (W + 2 * pad - k) / stride + 1;
     GX_CHECK_ARG(g->Ho > 0 && g->Wo > 0, "%s: empty output", name);
@@ -271,6 +273,11 @@ int wgrad_splits(const IG& g) {
     if (nsplit > nchunks) nsplit = nchunks;
     if (nsplit > 256) nsplit = 256;
     return nsplit < 1 ? 1 : nsplit;
+}
+
+// the record of a forward / data-gradient launch of this file (gx_conv_last_plan): the grid and the split the launch is handed
+void ig_note(int family, const dim3& grid, int nsplit, int chunks_per_split) {
+    gx_conv_plan_note({family, 0, 0, 0, 0, 0, BN, 0, 0, 0, 0, (int)grid.x, (int)grid.y, (int)grid.z, nsplit, chunks_per_split, 0, 0});
 }
 
 }  // namespace
@@ -523,6 +530,15 @@ conv3x3s2_wgrad_small_kernel(const float* __restrict__ x, const float* __restric
     }
 }
 
+// one instantiation of the stride-2 data gradient and its record: lG = log2 CIB, nq = UB, 256 (image, 2 x 2 block) threads per workgroup
+template <int CIB, int UB>
+static void s2_dgrad_launch(const dim3& grid, hipStream_t s, const float* dy, const float* w, float* dx, int N, int Cin, int Cout, int H,
+                            int W, int cin_n, int dxC) {
+    gx_conv_plan_note({GX_PLAN_S2_DG, 0, 0, 0, CIB == 2 ? 1 : 2, UB, 256, 0, 0, 0, 0, (int)grid.x, (int)grid.y, 0, 0, 0, 0, 0});
+    hipLaunchKernelGGL((conv3x3s2_dgrad_small_kernel<CIB, UB>), grid, dim3(256), (size_t)Cout * CIB * 12 * 4, s, dy, w, dx, N, Cin, Cout, H, W,
+                       cin_n, dxC);
+}
+
 extern "C" {
 
 size_t gx_conv3x3s2_wgrad_small_ws_bytes(int N, int Cin, int Cout, int H, int W) {
@@ -534,10 +550,11 @@ size_t gx_conv3x3s2_wgrad_small_ws_bytes(int N, int Cin, int Cout, int H, int W)
  * [N,Cout,H/2,W/2]; ws: gx_conv3x3s2_wgrad_small_ws_bytes. */
 int gx_conv3x3s2_wgrad_small(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int H, int W, void* ws,
                              size_t ws_bytes, gx_stream_t stream) {
-    GX_CHECK_ARG(x && dy && dw && ws, "gx_conv3x3s2_wgrad_small: null pointer");
+    // (the shape and the workspace size before the pointers: a refusal needs no memory to be decided)
     GX_CHECK_ARG(N > 0 && Cin > 0 && Cout > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && Cin <= 65535,
                  "gx_conv3x3s2_wgrad_small: even H, W");
     GX_CHECK_ARG(ws_bytes >= gx_conv3x3s2_wgrad_small_ws_bytes(N, Cin, Cout, H, W), "gx_conv3x3s2_wgrad_small: workspace too small");
+    GX_CHECK_ARG(x && dy && dw && ws, "gx_conv3x3s2_wgrad_small: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int P = N * (H / 2) * (W / 2);
     const int blocks = Cin * gx_ceil_div(Cout, 8);
@@ -573,10 +590,10 @@ int gx_conv3x3s2_dgrad_small_ex(const float* dy, const float* w, float* dx, int 
                                 int dx_channels, gx_stream_t stream) {
     GX_CHECK_ARG(dx_channels >= cin_n, "gx_conv3x3s2_dgrad_small_ex: dx_channels (%d) < cin_n (%d)", dx_channels, cin_n);
     const int dxC = dx_channels;
-    GX_CHECK_ARG(dy && w && dx, "gx_conv3x3s2_dgrad_small: null pointer");
     GX_CHECK_ARG(N > 0 && Cin > 0 && Cout > 0 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1) && (double)N * H * W < 4.0 * 256 * 65535,
                  "gx_conv3x3s2_dgrad_small: even H, W; N H W / 1024 <= 65535");
     GX_CHECK_ARG(cin_n >= 1 && cin_n <= Cin && Cout * 4 * 12 * 4 <= 64 * 1024, "gx_conv3x3s2_dgrad_small: 1 <= cin_n <= Cin, Cout <= 341");
+    GX_CHECK_ARG(dy && w && dx, "gx_conv3x3s2_dgrad_small: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int npix = (H / 2) * (W / 2);
     {
@@ -584,12 +601,12 @@ int gx_conv3x3s2_dgrad_small_ex(const float* dy, const float* w, float* dx, int 
         const bool few = (long)gx_ceil_div(cin_n, cin_n <= 2 ? 2 : 4) * gx_ceil_div(N * npix, 256) < 512;
         if (cin_n <= 2) {
             const dim3 grid(gx_ceil_div(cin_n, 2), gx_ceil_div(N * npix, 256));
-            if (few) hipLaunchKernelGGL((conv3x3s2_dgrad_small_kernel<2, 8>), grid, dim3(256), (size_t)Cout * 2 * 12 * 4, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
-            else hipLaunchKernelGGL((conv3x3s2_dgrad_small_kernel<2, 1>), grid, dim3(256), (size_t)Cout * 2 * 12 * 4, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
+            if (few) s2_dgrad_launch<2, 8>(grid, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
+            else s2_dgrad_launch<2, 1>(grid, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
         } else {
             const dim3 grid(gx_ceil_div(cin_n, 4), gx_ceil_div(N * npix, 256));
-            if (few) hipLaunchKernelGGL((conv3x3s2_dgrad_small_kernel<4, 8>), grid, dim3(256), (size_t)Cout * 4 * 12 * 4, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
-            else hipLaunchKernelGGL((conv3x3s2_dgrad_small_kernel<4, 1>), grid, dim3(256), (size_t)Cout * 4 * 12 * 4, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
+            if (few) s2_dgrad_launch<4, 8>(grid, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
+            else s2_dgrad_launch<4, 1>(grid, s, dy, w, dx, N, Cin, Cout, H, W, cin_n, dxC);
         }
     }
     GX_CHECK_LAUNCH("gx_conv3x3s2_dgrad_small");
@@ -606,10 +623,10 @@ size_t gx_conv2d_direct_fwd_ws_bytes(int N, int Cin, int Cout, int H, int W, int
 int gx_conv2d_direct_fwd_ws(const float* x, const float* w, const float* bias, int act, float* y, int N, int Cin,
                             int Cout, int H, int W, int k, int stride, int pad, void* ws, size_t ws_bytes,
                             gx_stream_t stream) {
-    GX_CHECK_ARG(x && w && y && act >= 0 && act <= 2, "gx_conv2d_direct_fwd: null pointer / bad act");
     IG g;
     int rc = ig_geom("gx_conv2d_direct_fwd", &g, 0, N, Cin, Cout, H, W, k, stride, pad);
     if (rc) return rc;
+    GX_CHECK_ARG(x && w && y && act >= 0 && act <= 2, "gx_conv2d_direct_fwd: null pointer / bad act");
     const int ns = fwd_splits(g);
     if (ns <= 1 || !ws || ws_bytes < (size_t)ns * g.M * g.Ncols * sizeof(float))
         return gx_conv2d_direct_fwd(x, w, bias, act, y, N, Cin, Cout, H, W, k, stride, pad, stream);
@@ -617,8 +634,9 @@ int gx_conv2d_direct_fwd_ws(const float* x, const float* w, const float* bias, i
     g.chunks_per_split = gx_ceil_div(gx_ceil_div(g.K, BK), ns);
     {
         GxProf pf(KID_DCONV, s, 2.0 * N * Cout * Cin * k * k * g.Ho * g.Wo, 4.0 * N * (Cin * H * W + Cout * g.Ho * g.Wo));
-        hipLaunchKernelGGL(igemm_kernel<0>, dim3(gx_ceil_div(g.Ncols, BN), gx_ceil_div(g.M, BM), ns), dim3(256), 0, s, w,
-                           x, (const float*)nullptr, 0, (float*)ws, g);
+        const dim3 grid(gx_ceil_div(g.Ncols, BN), gx_ceil_div(g.M, BM), ns);
+        ig_note(GX_PLAN_IGEMM_FWD, grid, ns, g.chunks_per_split);
+        hipLaunchKernelGGL(igemm_kernel<0>, grid, dim3(256), 0, s, w, x, (const float*)nullptr, 0, (float*)ws, g);
     }
     GX_CHECK_LAUNCH("gx_conv2d_direct_fwd(split)");
     {
@@ -633,22 +651,24 @@ int gx_conv2d_direct_fwd_ws(const float* x, const float* w, const float* bias, i
 
 int gx_conv2d_direct_fwd(const float* x, const float* w, const float* bias, int act, float* y, int N, int Cin,
                          int Cout, int H, int W, int k, int stride, int pad, gx_stream_t stream) {
-    GX_CHECK_ARG(x && w && y && act >= 0 && act <= 2, "gx_conv2d_direct_fwd: null pointer / bad act");
     IG g;
     int rc = ig_geom("gx_conv2d_direct_fwd", &g, 0, N, Cin, Cout, H, W, k, stride, pad);
     if (rc) return rc;
+    GX_CHECK_ARG(x && w && y && act >= 0 && act <= 2, "gx_conv2d_direct_fwd: null pointer / bad act");
     hipStream_t s = (hipStream_t)stream;
     if (fwd_small_ok(N, Cin, Cout, H, W, k, stride, pad)) {      // the ComponentVAE encoder's chip-filling layers: vector ALUs
         GxProf pf(KID_DCONV, s, 2.0 * N * Cout * Cin * k * k * g.Ho * g.Wo, 4.0 * N * (Cin * H * W + Cout * g.Ho * g.Wo));
-        hipLaunchKernelGGL(conv3x3s2_fwd_small_kernel<8>, dim3(gx_ceil_div(Cout, 8), gx_ceil_div(N * (H / 2) * (W / 2), 256)), dim3(256),
-                           (size_t)Cin * 8 * 12 * 4, s, x, w, bias, act, y, N, Cin, Cout, H, W);
+        const dim3 grid(gx_ceil_div(Cout, 8), gx_ceil_div(N * (H / 2) * (W / 2), 256));
+        gx_conv_plan_note({GX_PLAN_S2_FWD, 0, 0, 0, 0, 0, 256, 0, 0, 0, 0, (int)grid.x, (int)grid.y, 0, 0, 0, 0, 0});
+        hipLaunchKernelGGL(conv3x3s2_fwd_small_kernel<8>, grid, dim3(256), (size_t)Cin * 8 * 12 * 4, s, x, w, bias, act, y, N, Cin, Cout, H, W);
         GX_CHECK_LAUNCH("gx_conv2d_direct_fwd(small)");
         return GX_OK;
     }
     {
         GxProf pf(KID_DCONV, s, 2.0 * N * Cout * Cin * k * k * g.Ho * g.Wo, 4.0 * N * (Cin * H * W + Cout * g.Ho * g.Wo));
-        hipLaunchKernelGGL(igemm_kernel<0>, dim3(gx_ceil_div(g.Ncols, BN), gx_ceil_div(g.M, BM), 1), dim3(256), 0, s, w,
-                           x, bias, act, y, g);
+        const dim3 grid(gx_ceil_div(g.Ncols, BN), gx_ceil_div(g.M, BM), 1);
+        ig_note(GX_PLAN_IGEMM_FWD, grid, 1, g.chunks_per_split);
+        hipLaunchKernelGGL(igemm_kernel<0>, grid, dim3(256), 0, s, w, x, bias, act, y, g);
     }
     GX_CHECK_LAUNCH("gx_conv2d_direct_fwd");
     return GX_OK;
@@ -656,15 +676,16 @@ int gx_conv2d_direct_fwd(const float* x, const float* w, const float* bias, int 
 
 int gx_conv2d_direct_dgrad(const float* dy, const float* w, float* dx, int N, int Cin, int Cout, int H, int W, int k,
                            int stride, int pad, gx_stream_t stream) {
-    GX_CHECK_ARG(dy && w && dx, "gx_conv2d_direct_dgrad: null pointer");
     IG g;
     int rc = ig_geom("gx_conv2d_direct_dgrad", &g, 1, N, Cin, Cout, H, W, k, stride, pad);
     if (rc) return rc;
+    GX_CHECK_ARG(dy && w && dx, "gx_conv2d_direct_dgrad: null pointer");
     hipStream_t s = (hipStream_t)stream;
     {
         GxProf pf(KID_DCONV, s, 2.0 * N * Cout * Cin * k * k * g.Ho * g.Wo, 4.0 * N * (Cin * H * W + Cout * g.Ho * g.Wo));
-        hipLaunchKernelGGL(igemm_kernel<1>, dim3(gx_ceil_div(g.Ncols, BN), gx_ceil_div(g.M, BM), 1), dim3(256), 0, s, w,
-                           dy, (const float*)nullptr, 0, dx, g);
+        const dim3 grid(gx_ceil_div(g.Ncols, BN), gx_ceil_div(g.M, BM), 1);
+        ig_note(GX_PLAN_IGEMM_DG, grid, 1, g.chunks_per_split);
+        hipLaunchKernelGGL(igemm_kernel<1>, grid, dim3(256), 0, s, w, dy, (const float*)nullptr, 0, dx, g);
     }
     GX_CHECK_LAUNCH("gx_conv2d_direct_dgrad");
     return GX_OK;
@@ -678,12 +699,12 @@ size_t gx_conv2d_direct_wgrad_ws_bytes(int N, int Cin, int Cout, int H, int W, i
 
 int gx_conv2d_direct_wgrad(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int H, int W, int k,
                            int stride, int pad, void* ws, size_t ws_bytes, gx_stream_t stream) {
-    GX_CHECK_ARG(x && dy && dw && ws, "gx_conv2d_direct_wgrad: null pointer");
     IG g;
     int rc = ig_geom("gx_conv2d_direct_wgrad", &g, 2, N, Cin, Cout, H, W, k, stride, pad);
     if (rc) return rc;
     const int nsplit = wgrad_splits(g);
     GX_CHECK_ARG(ws_bytes >= (size_t)nsplit * g.M * g.Ncols * sizeof(float), "gx_conv2d_direct_wgrad: workspace too small");
+    GX_CHECK_ARG(x && dy && dw && ws, "gx_conv2d_direct_wgrad: null pointer");
     g.chunks_per_split = gx_ceil_div(gx_ceil_div(g.K, BK), nsplit);
     const int zs = gx_ceil_div(gx_ceil_div(g.K, BK), g.chunks_per_split);
     hipStream_t s = (hipStream_t)stream;

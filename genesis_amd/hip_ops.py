@@ -287,7 +287,7 @@ def defer_discard():
 PLAN_FIELDS = ('family', 'form', 'lTH', 'lTW', 'lG', 'nq', 'pixels', 'rt_th', 'rt_tw', 'tiles_h', 'tiles_w', 'grid_x', 'grid_y',
                'grid_z', 'nsplit', 'chunks_per_split', 'nfull', 'stats')          # the GX_PLAN_* indices of include/genesis_hip.h
 PLAN_FAMILIES = ('none', 'tap_c3', 'tap_dt', 'tap_dg', 'tap_c5', 'kq_c3', 'kq_dt', 'kq_dg', 'kq_c3h', 'kq_dth', 'kq_dgh', 'kq_c5h',
-                 'wino', 'smallcin')                                              # GX_PLAN_NONE ... GX_PLAN_SMALLCIN
+                 'wino', 'smallcin', 'igemm_fwd', 'igemm_dg', 's2_fwd', 's2_dg')  # GX_PLAN_NONE ... GX_PLAN_S2_DG
 PLAN_FORMS = ('fp32', 'bf16x6', 'fp16x3', 'bf16x1')
 
 
@@ -932,11 +932,33 @@ def conv3x3_dgrad_act(dy, w, xout, act, dbias_out=None, want_dbias=True, amax_in
     return dxa, dbias
 
 
+def _direct_geom(name, w, Cin, H, W, stride, pad, k=None):
+    """(Cout, k, Ho, Wo) of a generic direct conv, after the checks the C entry points cannot make (they see pointers, not
+    shapes): the weight is [Cout, Cin, k, k] for this input's Cin, the kernel is square, the output is not empty."""
+    if w is not None:
+        if w.dim() != 4 or w.shape[2] != w.shape[3]:
+            raise GenesisHipError('%s: the weight must be [Cout, Cin, k, k] with a square kernel, got %s' % (name, tuple(w.shape)))
+        if w.shape[1] != Cin:
+            raise GenesisHipError('%s: the weight %s has %d input channels, the tensor %d' % (name, tuple(w.shape), w.shape[1], Cin))
+        k = w.shape[2]
+    if stride < 1 or pad < 0 or H + 2 * pad < k or W + 2 * pad < k:
+        raise GenesisHipError('%s: empty output (H %d, W %d, k %d, stride %d, pad %d)' % (name, H, W, k, stride, pad))
+    return (w.shape[0] if w is not None else None), k, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def _want_shape(name, what, t, shape):
+    if tuple(t.shape) != tuple(shape):
+        raise GenesisHipError('%s: %s is %s, the geometry says %s' % (name, what, tuple(t.shape), tuple(shape)))
+
+
 def conv2d_direct_fwd(x, w, bias, act, stride, pad):
     _chk(x, 'conv2d_direct.x'); _chk(w, 'conv2d_direct.w'); _chk(bias, 'conv2d_direct.bias')
+    if x.dim() != 4:
+        raise GenesisHipError('conv2d_direct_fwd: x must be [N, Cin, H, W], got %s' % (tuple(x.shape),))
     N, Cin, H, W = x.shape
-    Cout, _, k, _ = w.shape
-    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    Cout, k, Ho, Wo = _direct_geom('conv2d_direct_fwd', w, Cin, H, W, stride, pad)
+    if bias is not None:
+        _want_shape('conv2d_direct_fwd', 'bias', bias, (Cout,))
     y = torch.empty(N, Cout, Ho, Wo, dtype=F32, device=x.device)
     nb = _lib.query('gx_conv2d_direct_fwd_ws_bytes', N, Cin, Cout, H, W, k, stride, pad)
     ws = _ws(nb, x.device) if nb else None          # (under-filled grids split the contraction: partial slabs)
@@ -948,8 +970,11 @@ def conv2d_direct_fwd(x, w, bias, act, stride, pad):
 
 def conv2d_direct_dgrad(dy, w, H, W, stride, pad):
     _chk(dy, 'conv2d_direct_dgrad.dy'); _chk(w, 'conv2d_direct_dgrad.w')
-    N = dy.shape[0]
-    Cout, Cin, k, _ = w.shape
+    if w.dim() != 4 or dy.dim() != 4:
+        raise GenesisHipError('conv2d_direct_dgrad: dy %s / w %s must be 4-D' % (tuple(dy.shape), tuple(w.shape)))
+    N, Cin = dy.shape[0], w.shape[1]
+    Cout, k, Ho, Wo = _direct_geom('conv2d_direct_dgrad', w, Cin, H, W, stride, pad)
+    _want_shape('conv2d_direct_dgrad', 'dy', dy, (N, Cout, Ho, Wo))
     dx = torch.empty(N, Cin, H, W, dtype=F32, device=dy.device)
     _lib.call('gx_conv2d_direct_dgrad', _p(dy), _p(w), _p(dx), N, Cin, Cout, H, W, k, stride, pad, _stream())
     return dx
@@ -967,11 +992,29 @@ def mask_image_stack(mask, x):
     return out
 
 
+def _s2_geom(name, w, dy, N, Cin, H, W):
+    """The conv3x3 stride 2 pad 1 kernels' shapes: w [Cout, Cin, 3, 3] (w None: Cout from dy), even H and W, dy [N, Cout, H/2, W/2]."""
+    if w is not None and (w.dim() != 4 or tuple(w.shape[2:]) != (3, 3)):
+        raise GenesisHipError('%s: the weight must be [Cout, Cin, 3, 3], got %s' % (name, tuple(w.shape)))
+    if w is not None and Cin is not None and w.shape[1] != Cin:
+        raise GenesisHipError('%s: the weight %s has %d input channels, the tensor %d' % (name, tuple(w.shape), w.shape[1], Cin))
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise GenesisHipError('%s: even H, W (got %d x %d)' % (name, H, W))
+    if dy.dim() != 4:
+        raise GenesisHipError('%s: dy must be [N, Cout, H/2, W/2], got %s' % (name, tuple(dy.shape)))
+    Cout = w.shape[0] if w is not None else dy.shape[1]
+    _want_shape(name, 'dy', dy, (N, Cout, H // 2, W // 2))
+    return Cout
+
+
 def conv3x3s2_dgrad_lead(dy, w, H, W, cin_n):
     """The compact gradient [N,cin_n,H,W] of the first cin_n input channels of a conv3x3 stride 2 pad 1 (gx_conv3x3s2_dgrad_small_ex)."""
     _chk(dy, 'conv3x3s2_dgrad.dy'); _chk(w, 'conv3x3s2_dgrad.w')
     N = dy.shape[0]
+    _s2_geom('conv3x3s2_dgrad_lead', w, dy, N, None, H, W)
     Cout, Cin = w.shape[0], w.shape[1]
+    if not 1 <= int(cin_n) <= Cin:
+        raise GenesisHipError('conv3x3s2_dgrad_lead: 1 <= cin_n <= Cin (%d), got %d' % (Cin, cin_n))
     dx = torch.empty(N, cin_n, H, W, dtype=F32, device=dy.device)
     _lib.call('gx_conv3x3s2_dgrad_small_ex', _p(dy), _p(w), _p(dx), N, Cin, Cout, H, W, int(cin_n), int(cin_n), _stream())
     return dx
@@ -982,8 +1025,11 @@ def conv3x3s2_dgrad_small(dy, w, H, W, cin_n=None):
     others are zero (gx_conv3x3s2_dgrad_small)."""
     _chk(dy, 'conv3x3s2_dgrad.dy'); _chk(w, 'conv3x3s2_dgrad.w')
     N = dy.shape[0]
+    _s2_geom('conv3x3s2_dgrad_small', w, dy, N, None, H, W)
     Cout, Cin = w.shape[0], w.shape[1]
     cin_n = Cin if cin_n is None else int(cin_n)
+    if not 1 <= cin_n <= Cin:
+        raise GenesisHipError('conv3x3s2_dgrad_small: 1 <= cin_n <= Cin (%d), got %d' % (Cin, cin_n))
     dx = (torch.empty if cin_n == Cin else torch.zeros)(N, Cin, H, W, dtype=F32, device=dy.device)
     _lib.call('gx_conv3x3s2_dgrad_small', _p(dy), _p(w), _p(dx), N, Cin, Cout, H, W, cin_n, _stream())
     return dx
@@ -992,9 +1038,13 @@ def conv3x3s2_dgrad_small(dy, w, H, W, cin_n=None):
 def conv3x3s2_wgrad_small(x, dy, out=None):
     """dw [Cout,Cin,3,3] of a conv3x3 stride 2 pad 1 (even H, W) on the vector ALUs (gx_conv3x3s2_wgrad_small)."""
     _chk(x, 'conv3x3s2_wgrad.x'); _chk(dy, 'conv3x3s2_wgrad.dy')
+    if x.dim() != 4:
+        raise GenesisHipError('conv3x3s2_wgrad_small: x must be [N, Cin, H, W], got %s' % (tuple(x.shape),))
     N, Cin, H, W = x.shape
-    Cout = dy.shape[1]
-    assert tuple(dy.shape) == (N, Cout, H // 2, W // 2), (x.shape, dy.shape)
+    Cout = _s2_geom('conv3x3s2_wgrad_small', None, dy, N, Cin, H, W)
+    if out is not None:
+        _chk(out, 'conv3x3s2_wgrad.out')
+        _want_shape('conv3x3s2_wgrad_small', 'out', out, (Cout, Cin, 3, 3))
     dw = out if out is not None else torch.empty(Cout, Cin, 3, 3, dtype=F32, device=x.device)
     nb = _lib.query('gx_conv3x3s2_wgrad_small_ws_bytes', N, Cin, Cout, H, W)
     ws = _ws(nb, x.device)
@@ -1004,8 +1054,15 @@ def conv3x3s2_wgrad_small(x, dy, out=None):
 
 def conv2d_direct_wgrad(x, dy, k, stride, pad, out=None):
     _chk(x, 'conv2d_direct_wgrad.x'); _chk(dy, 'conv2d_direct_wgrad.dy')
+    if x.dim() != 4 or dy.dim() != 4:
+        raise GenesisHipError('conv2d_direct_wgrad: x %s / dy %s must be 4-D' % (tuple(x.shape), tuple(dy.shape)))
     N, Cin, H, W = x.shape
     Cout = dy.shape[1]
+    _, _, Ho, Wo = _direct_geom('conv2d_direct_wgrad', None, Cin, H, W, stride, pad, k=k)
+    _want_shape('conv2d_direct_wgrad', 'dy', dy, (N, Cout, Ho, Wo))
+    if out is not None:
+        _chk(out, 'conv2d_direct_wgrad.out')
+        _want_shape('conv2d_direct_wgrad', 'out', out, (Cout, Cin, k, k))
     dw = out if out is not None else torch.empty(Cout, Cin, k, k, dtype=F32, device=x.device)
     nb = _lib.query('gx_conv2d_direct_wgrad_ws_bytes', N, Cin, Cout, H, W, k, stride, pad)
     ws = _ws(nb, x.device)

@@ -160,14 +160,15 @@ int gx_tapconv_precision(int mode);
 int gx_tapconv_precision_get(void);
 int gx_tapconv_last_mode(void);
 /*      gx_conv_last_plan(out, n): the tile plan of this thread's most recent forward / data-gradient conv launch (the tap-conv
- *      kernels, the input-layer kernel of gx_conv3x3_fwd, every gx_kq.hip conv kernel, Winograd), written by the launcher on the
+ *      kernels, the input-layer kernel of gx_conv3x3_fwd, every gx_kq.hip conv kernel, Winograd, the generic strided conv and the
+ *      stride-2 vector-ALU kernels of gx_igemm.hip), written by the launcher on the
  *      host just before it launches, every field copied from the values the launch itself uses.  Fills out[0 .. min(n,
  *      GX_PLAN_FIELDS)) in the order of the GX_PLAN_* indices below and returns GX_PLAN_FIELDS; before any such launch the family
  *      is GX_PLAN_NONE and every other field 0.  A field the family does not have is 0.  Helper launches (weight packing, amax
  *      passes, split-K reduces) leave the record alone.  For tests and diagnosis: no synchronisation, no device work. */
 #define GX_PLAN_FIELDS 18
 /*      out[] indices */
-#define GX_PLAN_FAMILY 0          /* GX_PLAN_NONE ... GX_PLAN_SMALLCIN */
+#define GX_PLAN_FAMILY 0          /* GX_PLAN_NONE ... GX_PLAN_S2_DG */
 #define GX_PLAN_FORM 1            /* operands: 0 fp32, 1 bf16 x 6, 2 fp16 x 3, 3 bf16 x 1 */
 #define GX_PLAN_LTH 2             /* log2 of the tile's height, width and images per tile */
 #define GX_PLAN_LTW 3
@@ -200,6 +201,14 @@ int gx_tapconv_last_mode(void);
 #define GX_PLAN_KQ_C5H 11         /* kq_c5h_kernel */
 #define GX_PLAN_WINO 12           /* wino_conv_kernel / wino_conv_h_kernel */
 #define GX_PLAN_SMALLCIN 13       /* conv3x3_smallcin_fwd_kernel */
+/*      gx_igemm.hip (form fp32): the implicit-GEMM families record pixels = 128 (the tile's columns), the grid, nsplit (1: the single-
+ *      launch form) and the 16-wide contraction chunks per slab; the stride-2 vector-ALU kernels pixels = 256 (threads) and
+ *      grid_x / grid_y, the data gradient also lG = log2 CIB (input channels per thread) and nq = UB (dy channels loaded ahead).  The
+ *      weight gradients and the reduce launches note nothing. */
+#define GX_PLAN_IGEMM_FWD 14      /* igemm_kernel<0>: gx_conv2d_direct_fwd / _fwd_ws */
+#define GX_PLAN_IGEMM_DG 15       /* igemm_kernel<1>: gx_conv2d_direct_dgrad */
+#define GX_PLAN_S2_FWD 16         /* conv3x3s2_fwd_small_kernel */
+#define GX_PLAN_S2_DG 17          /* conv3x3s2_dgrad_small_kernel */
 int gx_conv_last_plan(int* out, int n);
 /*      Mode 2's per-tensor maximum without a second pass over the tensor: gx_kq_amax_link(parts, capacity, numel) arms a one-shot,
  *      per-thread hand-over -- the next producer that supports it (the register-resident GroupNorm + ReLU kernels behind gx_gn_relu_fwd_parts /
