@@ -9,6 +9,7 @@ import re
 # torch bundles its own libamdhip64.so.7; import it FIRST so that libgenesis_hip.so (same SONAME dependency)
 # binds to the HIP runtime torch's streams and allocations live in, not to a second copy from /opt/rocm.
 import torch  # noqa: F401
+import numpy as np
 
 _HERE = osp.dirname(osp.abspath(__file__))
 # GENESIS_HIP_LIB: an alternative build of the same library (kernel experiments: tools/abl_build.sh)
@@ -98,6 +99,19 @@ def call(name, *args):
 def query(name, *args):
     """Calls a size_t-returning *_ws_bytes query."""
     return int(getattr(load(), name)(*args))
+
+
+def as_u8(data, what):
+    """bytes / a uint8 array -> a contiguous 1-D uint8 array for a C call; `what` prefixes the refusal."""
+    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+        raise GenesisHipError('%s: expected bytes or a contiguous 1-D uint8 array' % what)
+    return a
+
+
+def np_ptr(a, offset=0):
+    """The address of a numpy array's data, `offset` bytes in, as a C pointer argument."""
+    return ctypes.c_void_p(a.ctypes.data + int(offset))
 
 
 def current_ctx():

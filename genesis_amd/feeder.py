@@ -4,12 +4,12 @@ to the GPU inside the training loop (train.py:218-220).  Here the uint8 HWC fram
 on a side stream one batch ahead (a ring of slots) and converted to the fp32 NCHW batch in [0,1] by one HIP launch, so
 the step after compute does not wait on the host."""
 import ctypes
-import time
 
 import torch
 
 from . import _lib
 from ._lib import GenesisHipError
+from .loading import host_wait
 
 
 def u8hwc_to_f32chw(frames_u8, img_size=None, out=None):
@@ -323,12 +323,6 @@ class DeviceFeeder(object):
         self.tail = 0                        # slot the next prefetch fills
         self._prefetch()
 
-    @staticmethod
-    def _host_wait(ev):
-        if ev is not None:
-            while not ev.query():
-                time.sleep(2e-4)
-
     def _prefetch(self):
         try:
             nxt = next(self.it)
@@ -368,13 +362,13 @@ class DeviceFeeder(object):
         if t.dtype != torch.uint8 or t.dim() != 4:
             raise GenesisHipError('feeder: host batches must be uint8 [B,H,W,C]')
         s = self.tail
-        self._host_wait(self.ready[s])       # pinned[s] is free: its previous copy has executed
-        self._host_wait(self.consumed[s])    # dev_u8[s] is free: the conversion kernel that read it has run
+        host_wait(self.ready[s])       # pinned[s] is free: its previous copy has executed
+        host_wait(self.consumed[s])    # dev_u8[s] is free: the conversion kernel that read it has run
         if lab is not None and (self.pinned_lab[s] is None or self.pinned_lab[s].shape != lab.shape
                                 or self.pinned_lab[s].dtype != lab.dtype):
             for q in range(self.depth):      # the label ring likewise, all at once
                 if self.pinned_lab[q] is None or self.pinned_lab[q].shape != lab.shape or self.pinned_lab[q].dtype != lab.dtype:
-                    self._host_wait(self.ready[q]); self._host_wait(self.consumed[q])
+                    host_wait(self.ready[q]); host_wait(self.consumed[q])
                     self.pinned_lab[q] = torch.empty(lab.shape, dtype=lab.dtype, pin_memory=True)
                     self.dev_lab[q] = torch.empty(lab.shape, dtype=lab.dtype, device=self.device)
         if self.pinned[s] is None or self.pinned[s].shape != t.shape:
@@ -383,7 +377,7 @@ class DeviceFeeder(object):
             # segment to get ahead again: 1.5 k -> 2.8 k -> 6.1 k img/s over the first 300 steps, measured)
             for q in range(self.depth):
                 if self.pinned[q] is None or self.pinned[q].shape != t.shape:
-                    self._host_wait(self.ready[q]); self._host_wait(self.consumed[q])
+                    host_wait(self.ready[q]); host_wait(self.consumed[q])
                     self.pinned[q] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
                     self.dev_u8[q] = torch.empty(t.shape, dtype=torch.uint8, device=self.device)
         self.pinned[s].copy_(t)

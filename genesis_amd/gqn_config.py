@@ -34,7 +34,6 @@ import ctypes
 import os
 import queue
 import threading
-import time
 
 import numpy as np
 import torch
@@ -48,6 +47,7 @@ from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import _lib, jpeg, tfrecord  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
+from genesis_amd.loading import MAX_WORKERS, host_wait, parse_shard  # noqa: E402
 from genesis_amd.tfrecord import TFRecordError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/gqn_datasets', 'Path to data folder.')
@@ -62,7 +62,6 @@ TRAIN_FILES = 2160
 TEST_FILES = 240
 RECORDS_PER_FILE = 5000            # 2160 x 5000 = 10.8 M, 240 x 5000 = 1.2 M: the reference's hard-coded sizes
 FRAMES_PER_RECORD = 10
-MAX_WORKERS = 16
 CHUNK_RECORDS = 32                 # consecutive records of one file the merger takes at a time
 MODES = ('train', 'test', 'devel_train', 'devel_val')
 
@@ -86,7 +85,7 @@ def file_list(data_folder, mode, val_frac, train_files=TRAIN_FILES, test_files=T
     digits = len(str(n))
     base = os.path.join(data_folder, DATASET, folder)
     files = [os.path.join(base, '%0*d-of-%0*d.tfrecord' % (digits, i + 1, digits, n)) for i in range(first, end)]
-    rank, world = _shard(shard)
+    rank, world = parse_shard(shard, 'gqn')
     return files[rank::world]
 
 
@@ -102,13 +101,6 @@ def num_frames(mode, val_frac, train_files=TRAIN_FILES, test_files=TEST_FILES, r
     if mode == 'devel_val':
         return train_sz // val_frac
     raise ValueError("Mode not known.")
-
-
-def _shard(shard):
-    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-    if not 0 <= rank < world:
-        raise GenesisHipError('gqn: shard must be (rank, world) with 0 <= rank < world, not %r' % (shard,))
-    return rank, world
 
 
 def frame_rng(seed, file_number):
@@ -373,12 +365,6 @@ class GQNLoader(object):
     def __len__(self):
         return self.length
 
-    @staticmethod
-    def _host_wait(ev):
-        if ev is not None:
-            while not ev.query():
-                time.sleep(2e-4)
-
     def _prefetch(self):
         self.pending = None
         try:
@@ -389,13 +375,13 @@ class GQNLoader(object):
             self.copy_stream = torch.cuda.Stream(device=self.device)
         if b['geometry'] != self.geometry:              # the whole ring at once, the first time (feeder.py)
             for q in range(self.depth):
-                self._host_wait(self.ready[q]); self._host_wait(self.consumed[q])
+                host_wait(self.ready[q]); host_wait(self.consumed[q])
                 self.staging[q] = jpeg.JpegStaging(self.batch_size, *b['geometry'])
                 self.dev[q] = torch.empty(self.staging[q].nbytes, dtype=torch.uint8, device=self.device)
             self.geometry = b['geometry']
         s = self.slot
-        self._host_wait(self.ready[s])
-        self._host_wait(self.consumed[s])
+        host_wait(self.ready[s])
+        host_wait(self.consumed[s])
         n = len(b['coef'])
         self.staging[s].coef[:n] = b['coef']
         self.staging[s].qtab[:n] = b['qtab']
@@ -446,7 +432,7 @@ def host_splits(cfg, frame=None, shard=None, shuffle=True, train_files=TRAIN_FIL
                 records_per_file=RECORDS_PER_FILE, frames_per_record=FRAMES_PER_RECORD):
     """((train, val, test) HostBatches, their record counts): the host streams behind load(), which need no GPU and
     read nothing until they are iterated."""
-    rank, world = _shard(shard)
+    rank, world = parse_shard(shard, 'gqn')
     seed = getattr(cfg, 'seed', 0)
     hosts, sizes = [], []
     for mode, batch_size, workers in (('devel_train', cfg.batch_size, cfg.num_workers), ('devel_val', cfg.batch_size, cfg.num_workers),

@@ -25,7 +25,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import imagefile  # noqa: E402
+from genesis_amd import imagefile, loading  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/images', 'Path to data folder.')
@@ -92,7 +92,7 @@ def load(cfg, shard=None, device='cuda', **unused_kwargs):
     del unused_kwargs
     if not os.path.isdir(cfg.data_folder):
         raise GenesisHipError('image_folder: data folder %s does not exist' % cfg.data_folder)
-    fprint('image_folder: %d reader threads' % min(cfg.num_workers, imagefile.MAX_WORKERS))
+    fprint('image_folder: %d reader threads' % min(cfg.num_workers, loading.MAX_WORKERS))
     loaders = []
     for mode in MODES:
         files = [os.path.join(cfg.data_folder, f) for f in split_files(cfg.data_folder, mode)]

@@ -20,19 +20,17 @@ are replicated to three channels and alpha is dropped, as Pillow's convert('RGB'
 and the transformed frames equal Pillow's bit for bit (tests/golden/imagefile_pil.npz).  EXIF orientation is ignored, as
 Pillow's open ignores it.  Accepted and rejected streams: include/genesis_hip.h."""
 import ctypes
+import functools
 import threading
-import time
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _lib, feeder, png
-from ._lib import GenesisHipError
+from . import _lib, feeder, loading, png
+from ._lib import GenesisHipError, np_ptr as _ptr
 
 MAX_DIM = 4096                              # kGxImageMaxDim (csrc/gx_common.h): the C entry points reject larger frames themselves
 MAX_SIZE = 1024                             # img_size, at most (gx_u8_resample_ragged_f32chw's bound on the window)
-MAX_WORKERS = 16
 PNG_MAGIC = b'\x89PNG\r\n\x1a\n'
 JPEG_MAGIC = b'\xff\xd8'
 SAMPLING_NAMES = ('4:4:4', '4:2:2', '4:2:0')
@@ -40,17 +38,6 @@ SAMPLING_NAMES = ('4:4:4', '4:2:2', '4:2:0')
 JPEGR_WORDS, PNGR_WORDS, RSR_WORDS = 10, 5, 14
 JPEGR_BLOCKS_PER_WG, JPEGR_TILE_H, JPEGR_TILE_W = 128, 16, 64
 _QTAB_BYTES = 384
-
-
-def _as_u8(data):
-    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
-        raise GenesisHipError('imagefile: expected bytes or a contiguous 1-D uint8 array')
-    return a
-
-
-def _ptr(a, offset=0):
-    return ctypes.c_void_p(a.ctypes.data + int(offset))
 
 
 def _round16(n):
@@ -74,7 +61,7 @@ class JpegInfoAny(object):
 
 def jpeg_info_any(data):
     """JpegInfoAny of a stream (bytes / uint8 array); raises GenesisHipError for what the decoder does not accept."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'imagefile')
     raw = np.zeros(8, dtype=np.int32)
     _lib.call('gx_jpeg_info_any', _ptr(a), a.size, _ptr(raw))
     return JpegInfoAny(raw)
@@ -84,7 +71,7 @@ def entropy_decode_any(data, coef, qtab):
     """Entropy-decodes one stream into coef (int16, at least blocks * 64 values) and qtab (uint16, 192 values): quantised
     coefficients in natural order, per component plane in block raster order; a grey frame has one plane.  -> JpegInfoAny.
     Host only; the C call runs without the GIL."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'imagefile')
     if coef.dtype != np.int16 or not coef.flags.c_contiguous or not coef.flags.writeable:
         raise GenesisHipError('imagefile: coef must be a writable C-contiguous int16 array')
     if qtab.dtype != np.uint16 or qtab.size < 192 or not qtab.flags.c_contiguous or not qtab.flags.writeable:
@@ -96,7 +83,7 @@ def entropy_decode_any(data, coef, qtab):
 
 def stream_kind(data):
     """'png' or 'jpeg' from the magic bytes of a stream (never from a file name)."""
-    head = bytes(_as_u8(data)[:8])
+    head = bytes(_lib.as_u8(data, 'imagefile')[:8])
     if head == PNG_MAGIC:
         return 'png'
     if head[:2] == JPEG_MAGIC:
@@ -194,7 +181,7 @@ def frame_need(data, S, max_side):
 def stage_frame(arena, data, S, max_side):
     """Reads one stream's header, takes its place in the arena, decodes the serial half into it and lays its window tables
     behind it.  -> _Frame.  Safe to call from several threads on one arena."""
-    data = _as_u8(data)
+    data = _lib.as_u8(data, 'imagefile')
     kind, info, payload, (h2, w2, tabs) = frame_need(data, S, max_side)
     tbytes = 4 * sum(t.size for t in tabs)
     at = arena.alloc(_round16(payload) + tbytes)
@@ -308,7 +295,7 @@ def decode_image_batch(streams, img_size, return_u8=False, out=None, device='cud
     Every call allocates its own pinned arena and decodes on the calling thread: a path for a handful of streams, evaluation
     and tests.  Training reads through ImageFileLoader."""
     S = _check_size(img_size)
-    streams = [_as_u8(s) for s in streams]
+    streams = [_lib.as_u8(s, 'imagefile') for s in streams]
     if not streams:
         raise GenesisHipError('imagefile: an empty batch')
     device = torch.device(device)
@@ -327,173 +314,44 @@ def decode_image_batch(streams, img_size, return_u8=False, out=None, device='cud
     return launch(arena, dev, L, frames, out, return_u8)
 
 
-def read_file(path):
-    with open(path, 'rb') as f:
-        return np.frombuffer(f.read(), dtype=np.uint8)
+class ImageFileLoader(loading.FileBatchLoader):
+    """Batches of image files on the device: {'input': fp32 [B, 3, S, S]}, S = img_size, under the module's transform.
+    Length, order, the short last batch, reseeding and how a bad file is reported: loading.FileBatchLoader.
+    shard=(rank, world) keeps every world-th file from the rank-th on.
 
-
-class ImageFileLoader(object):
-    """Batches of image files on the device: {'input': fp32 [B, 3, S, S]}, S = img_size, under the module's transform.  The
-    interface and the epoch semantics of png.PngFileLoader: `__len__` = ceil(files / batch_size) (the short last batch is
-    kept), `batch_size`, `__iter__` / `__next__` with StopIteration at the end of the epoch, after which the loader can be
-    iterated again.  Every epoch draws a fresh permutation of the files from one generator seeded with `seed`
-    (shuffle=False: file order); `order` holds the file indices of the epoch in progress; shard=(rank, world) keeps every
-    world-th file from the rank-th on.
-
-    `num_workers` reader threads (at most 16) read the files and run the C calls (without the GIL) straight into a pinned
-    arena of a ring of `depth`, up to depth - 1 batches ahead; per batch there is one copy on a side stream and the four
-    launches.  An arena holds batch_size frames of at most max_side x max_side (frame_bound): a frame above max_side raises
-    GenesisHipError naming the file and max_side.  A file that cannot be read or decoded raises GenesisHipError naming its
-    path, from the `__next__` that would have returned its batch: the batches before it are delivered, the epoch ends there
-    and the next `__iter__` starts a new one."""
+    The reader threads stage (stage_frame) into the pinned arena of a slot; per batch there is one copy of the arena's used
+    prefix and the four launches.  An arena holds batch_size frames of at most max_side x max_side (frame_bound): a frame
+    above max_side raises GenesisHipError naming the file and max_side."""
 
     def __init__(self, files, batch_size, img_size, shuffle=True, seed=0, num_workers=4, device='cuda', depth=3, max_side=1024,
                  shard=None, name='imagefile'):
-        if batch_size <= 0:
-            raise GenesisHipError('%s: batch_size must be positive, not %r' % (name, batch_size))
         if not isinstance(max_side, int) or not 0 < max_side <= MAX_DIM:
             raise GenesisHipError('%s: max_side must be an int in [1, %d], not %r' % (name, MAX_DIM, max_side))
-        rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-        if not 0 <= rank < world:
-            raise GenesisHipError('%s: shard must be (rank, world) with 0 <= rank < world, not %r' % (name, shard))
-        self.files = list(files)[rank::world]
-        self.batch_size = int(batch_size)
+        rank, world = loading.parse_shard(shard, name)
+        super().__init__(list(files)[rank::world], batch_size, shuffle, seed, num_workers, device, depth, name)
         self.img_size = _check_size(img_size)
         self.max_side = max_side
-        self.shuffle = bool(shuffle)
-        self.rng = np.random.RandomState(int(seed) % (1 << 32))
-        self.workers = max(1, min(int(num_workers), MAX_WORKERS))
-        self.device = torch.device(device)
-        self.depth = max(2, int(depth))
-        self.name = name
-        self.length = -(-len(self.files) // self.batch_size)
-        self.pool = None
-        self.arenas = self.dev = None
-        self.copy_stream = None
-        self.ready = [None] * self.depth
-        self.consumed = [None] * self.depth
-        self.jobs = {}                          # batch number -> futures
-        self.order = None
-        self.pending = None                     # (batch number, frames, layout) of the batch whose copy is in flight
-        self.count = 0
-        self.failed = None                      # a reader's error of the batch after the one just returned
 
-    def __len__(self):
-        return self.length
+    def _open_ring(self):
+        """-> (the arenas, their device copies)"""
+        if self.device.type != 'cuda':
+            raise GenesisHipError('%s: frames are decoded on the HIP device; there is no CPU path' % self.name)
+        nbytes = self.batch_size * frame_bound(self.max_side, self.img_size)
+        arenas = [Arena(self.batch_size, nbytes) for _ in range(self.depth)]
+        return arenas, [torch.empty(a.nbytes, dtype=torch.uint8, device=self.device) for a in arenas]
 
-    @staticmethod
-    def _host_wait(ev):
-        if ev is not None:
-            while not ev.query():
-                time.sleep(2e-4)
+    def _jobs(self, s, idx):
+        arena = self.ring[0][s]
+        arena.reset()
+        decode = functools.partial(stage_frame, arena, S=self.img_size, max_side=self.max_side)
+        return [(self.files[f], decode) for f in idx]
 
-    def _read(self, path, arena):
-        try:
-            return stage_frame(arena, read_file(path), self.img_size, self.max_side)
-        except (GenesisHipError, OSError) as e:
-            raise GenesisHipError('%s: %s: %s' % (self.name, path, e)) from None
+    def _stage(self, s, n, frames):
+        arenas, dev = self.ring
+        L = lay_out(arenas[s], frames, self.img_size)
+        dev[s][:L.used].copy_(arenas[s].buffer[:L.used], non_blocking=True)
+        return frames, L
 
-    def _ring(self):
-        if self.arenas is None:
-            if self.device.type != 'cuda':
-                raise GenesisHipError('%s: frames are decoded on the HIP device; there is no CPU path' % self.name)
-            nbytes = self.batch_size * frame_bound(self.max_side, self.img_size)
-            self.arenas = [Arena(self.batch_size, nbytes) for _ in range(self.depth)]
-            self.dev = [torch.empty(a.nbytes, dtype=torch.uint8, device=self.device) for a in self.arenas]
-            self.copy_stream = torch.cuda.Stream(device=self.device)
-            self.pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix=self.name + '_reader')
-
-    def _submit(self, k):
-        """Hands the files of batch k to the reader threads; they write into arena k % depth."""
-        if k >= self.length:
-            return
-        s = k % self.depth
-        self._host_wait(self.ready[s])                  # the arena's last copy has left the pinned buffer
-        self._host_wait(self.consumed[s])
-        self.arenas[s].reset()
-        idx = self.order[k * self.batch_size:(k + 1) * self.batch_size]
-        self.jobs[k] = [self.pool.submit(self._read, self.files[f], self.arenas[s]) for f in idx]
-
-    def _copy(self, k):
-        """Waits for the readers of batch k, writes its descriptor tables and starts its copy on the side stream."""
-        self.pending = None
-        if k >= self.length:
-            return
-        error, frames = None, []
-        for j in self.jobs.pop(k):
-            try:
-                frames.append(j.result())
-            except Exception as e:                      # noqa: BLE001  (whatever a reader raised: the epoch ends either way)
-                error = error or e
-        if error is not None:
-            self._drop()
-            raise error
-        s = k % self.depth
-        L = lay_out(self.arenas[s], frames, self.img_size)
-        with torch.cuda.stream(self.copy_stream):
-            self.dev[s][:L.used].copy_(self.arenas[s].buffer[:L.used], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.ready[s] = ev
-        self.pending = (k, frames, L)
-
-    def _drop(self):
-        for jobs in self.jobs.values():
-            for j in jobs:
-                j.cancel()
-        for jobs in self.jobs.values():
-            for j in jobs:
-                if not j.cancelled():
-                    try:
-                        j.result()
-                    except Exception:                   # noqa: BLE001  (the epoch is being dropped)
-                        pass
-        self.jobs = {}
-        self.order = None
-        self.pending = None
-
-    def __iter__(self):
-        if not self.files:
-            raise GenesisHipError('%s: no files' % self.name)
-        self._drop()                                    # an epoch that was left half way
-        self.failed = None
-        self._ring()
-        n = len(self.files)
-        self.order = self.rng.permutation(n) if self.shuffle else np.arange(n)
-        self.count = 0
-        for k in range(self.depth - 1):
-            self._submit(k)
-        self._copy(0)
-        return self
-
-    def __next__(self):
-        if self.failed is not None:
-            e, self.failed = self.failed, None
-            raise e
-        if self.order is None:
-            iter(self)
-        if self.pending is None:
-            self.order = None
-            raise StopIteration
-        k, frames, L = self.pending
-        s = k % self.depth
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(self.ready[s])
-        batch = {'input': launch(self.arenas[s], self.dev[s], L, frames)}
-        done = torch.cuda.Event()
-        done.record(cur)
-        self.consumed[s] = done
-        self.count += 1
-        self._submit(k + self.depth - 1)                # keeps the readers depth - 1 batches ahead ...
-        try:
-            self._copy(k + 1)                           # ... and the next batch's copy under the caller's step
-        except Exception as e:                          # noqa: BLE001
-            self.failed = e                             # batch k is good and is returned; the next call raises
-        return batch
-
-    def close(self):
-        self._drop()
-        if self.pool is not None:
-            self.pool.shutdown(wait=True)
-            self.pool = None
-            self.arenas = self.dev = None
+    def _batch(self, s, staged):
+        arenas, dev = self.ring
+        return {'input': launch(arenas[s], dev[s], staged[1], staged[0])}

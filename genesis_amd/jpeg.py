@@ -14,22 +14,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GenesisHipError
+from ._lib import GenesisHipError, np_ptr as _ptr
 
 MAX_DIM = 128                               # the kernel keeps a frame's three planes in LDS
 SAMPLING_NAMES = ('4:4:4', '4:2:2', '4:2:0')
 _QTAB = 192                                 # uint16 values of a frame's three tables
-
-
-def _as_u8(data):
-    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
-        raise GenesisHipError('jpeg: expected bytes or a contiguous 1-D uint8 array')
-    return a
-
-
-def _ptr(a, offset=0):
-    return ctypes.c_void_p(a.ctypes.data + int(offset))
 
 
 class JpegInfo(object):
@@ -53,7 +42,7 @@ class JpegInfo(object):
 
 def jpeg_info(data):
     """JpegInfo of a stream (bytes / uint8 array); raises GenesisHipError for what the decoder does not accept."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'jpeg')
     raw = np.zeros(8, dtype=np.int32)
     _lib.call('gx_jpeg_info', _ptr(a), a.size, _ptr(raw))
     return JpegInfo(raw)
@@ -70,7 +59,7 @@ def entropy_decode(data, coef, qtab):
     """Entropy-decodes one stream into coef (int16, at least blocks * 64 values) and qtab (uint16 [3, 64] or [192]):
     quantised coefficients in natural order, per component plane in block raster order.  -> JpegInfo.  Host only; the C
     call runs without the GIL."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'jpeg')
     if coef.dtype != np.int16 or not coef.flags.c_contiguous or not coef.flags.writeable:
         raise GenesisHipError('jpeg: coef must be a writable C-contiguous int16 array')
     if qtab.dtype != np.uint16 or qtab.size < _QTAB or not qtab.flags.c_contiguous or not qtab.flags.writeable:

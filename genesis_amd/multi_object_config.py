@@ -43,6 +43,7 @@ from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import tfrecord  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
+from genesis_amd.loading import parse_shard  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/multi-object-datasets', 'Path to data folder.')
 flags.DEFINE_string('dataset', 'objects_room', '{multi_dsprites, objects_room, clevr, tetrominoes}')
@@ -105,9 +106,7 @@ class HostBatches(object):
                  verify_crc=True):
         if batch_size <= 0:
             raise GenesisHipError('multi_object: batch_size must be positive, not %r' % (batch_size,))
-        rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-        if not 0 <= rank < world:
-            raise GenesisHipError('multi_object: shard must be (rank, world) with 0 <= rank < world, not %r' % (shard,))
+        rank, world = parse_shard(shard, 'multi_object')
         self.path = path
         self.frame = (int(frame[0]), int(frame[1]))
         self.entities = int(entities)

@@ -42,6 +42,7 @@ from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import feeder  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
+from genesis_amd.loading import host_wait, parse_shard  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/multi_dsprites/processed', 'Path to data folder.')
 flags.DEFINE_boolean('unique_colours', False, 'Dataset with unique colours.')
@@ -107,12 +108,6 @@ def narrow_uint8(chunk):
     return u8 if np.array_equal(u8, chunk) else None
 
 
-def _wait(event):
-    if event is not None:
-        while not event.query():
-            time.sleep(2e-4)
-
-
 def upload(array, device, narrow=False):
     """A host array (a memmap, or a strided view of one) -> a device tensor, in chunks of whole rows through two pinned
     buffers on the current stream.  narrow: to uint8, each chunk checked with narrow_uint8; returns None at the first chunk
@@ -130,7 +125,7 @@ def upload(array, device, narrow=False):
         b = min(a + rows, n)
         chunk = array[a:b]
         s = k % len(pinned)
-        _wait(copied[s])                           # the copy that last read this pinned buffer has run
+        host_wait(copied[s])                      # the copy that last read this pinned buffer has run
         if narrow:
             chunk = narrow_uint8(np.ascontiguousarray(chunk))
             if chunk is None:
@@ -157,9 +152,7 @@ class MultidLoader(object):
 
     def __init__(self, image_path, batch_size, img_size=64, load_instances=True, mem_map=False, seed=0, shard=None,
                  device='cuda'):
-        rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-        if not 0 <= rank < world:
-            raise GenesisHipError('multid: shard must be (rank, world) with 0 <= rank < world, not %r' % (shard,))
+        rank, world = parse_shard(shard, 'multid')
         if int(batch_size) <= 0:
             raise GenesisHipError('multid: batch_size must be positive, not %r' % (batch_size,))
         self.path = image_path
@@ -269,8 +262,8 @@ class _StagingRing(object):
         B = min(self.loader.batch_size, n - first)
         rows = self.loader.order[first:first + B]
         s = self.tail
-        _wait(self.ready[s])
-        _wait(self.consumed[s])
+        host_wait(self.ready[s])
+        host_wait(self.consumed[s])
         for a, pin in zip(self.arrays, self.pinned[s]):
             np.take(a, rows, axis=0, out=pin.numpy()[:B])
         with torch.cuda.stream(self.copy_stream):

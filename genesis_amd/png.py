@@ -9,29 +9,17 @@ The decoded bytes equal Pillow's.  Accepted and rejected streams: include/genesi
 
 PngFileLoader is the loader both PNG data configs (shapestacks_config.py, sketchy_config.py) are built on."""
 import ctypes
-import time
-from concurrent.futures import ThreadPoolExecutor
+import functools
 
 import numpy as np
 import torch
 
-from . import _lib, feeder
-from ._lib import GenesisHipError
+from . import _lib, feeder, loading
+from ._lib import GenesisHipError, np_ptr as _ptr
+from .loading import read_file
 
 MAX_DIM = 4096                              # kGxPngMaxDim (csrc/gx_common.h): the C entry points reject larger frames themselves
 PLANE_RULES = {'byte': 0, 'shapestacks_reference': 1, 'index': 2}
-MAX_WORKERS = 16
-
-
-def _as_u8(data):
-    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
-        raise GenesisHipError('png: expected bytes or a contiguous 1-D uint8 array')
-    return a
-
-
-def _ptr(a, offset=0):
-    return ctypes.c_void_p(a.ctypes.data + int(offset))
 
 
 class PngInfo(object):
@@ -53,7 +41,7 @@ class PngInfo(object):
 
 def png_info(data):
     """PngInfo of a stream (bytes / uint8 array); raises GenesisHipError for what the decoder does not accept."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'png')
     raw = np.zeros(8, dtype=np.int32)
     _lib.call('gx_png_info', _ptr(a), a.size, _ptr(raw))
     return PngInfo(raw)
@@ -67,7 +55,7 @@ def frame_bytes(H, W, C):
 def inflate(data, dst):
     """Checks one stream (signature, chunks, CRC-32s) and inflates its IDAT data into dst (uint8, at least the frame's
     frame_bytes): still filtered.  -> PngInfo.  Host only; the C call runs without the GIL."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'png')
     if dst.dtype != np.uint8 or not dst.flags.c_contiguous or not dst.flags.writeable:
         raise GenesisHipError('png: dst must be a writable C-contiguous uint8 array')
     raw = np.zeros(8, dtype=np.int32)
@@ -186,11 +174,6 @@ def decode_png_labels(streams, rule, size=None, crop=None, device='cuda'):
     return labels_staged(dev, staging.capacity, staging.capacity, staging.geometry, rule, size, crop)
 
 
-def read_file(path):
-    with open(path, 'rb') as f:
-        return np.frombuffer(f.read(), dtype=np.uint8)
-
-
 class _Ring(object):
     """`depth` pinned PngStaging slots of one geometry with their device copies."""
 
@@ -200,185 +183,55 @@ class _Ring(object):
         self.dev = [torch.empty(s.nbytes, dtype=torch.uint8, device=device) for s in self.staging]
 
 
-class PngFileLoader(object):
+class PngFileLoader(loading.FileBatchLoader):
     """Batches of PNG files on the device: {'input': fp32 [B, C, S_h, S_w]} and, with `map_files`, 'instances': int64
     [B, 1, S_h, S_w] (channel 0 of the map PNG of every frame after `label_rule`, cropped like the frame, nearest).
-    `__len__` = ceil(files / batch_size) (the reference's DataLoaders keep the short last batch), `batch_size`,
-    `__iter__` / `__next__` with StopIteration at the end of the epoch, after which the loader can be iterated again.
+    Length, order, the short last batch, reseeding and how a bad file is reported: loading.FileBatchLoader.
 
     crop is a window (top, left, h, w), or an int: the centre crop of that size (feeder.centre_box) of whatever size the
-    files have.  Every epoch draws a fresh permutation of the files from one generator seeded with `seed` (shuffle=False: file order).
-    `num_workers` reader threads (at most 16) read the files and inflate them (PngStaging.decode; the C call drops the GIL)
-    straight into a pinned slot of a ring, up to depth - 1 batches ahead; per batch and kind there is one copy on a side
-    stream and one gx_png_unfilter launch.  A file that cannot be read or decoded raises GenesisHipError naming its path,
-    from the `__next__` that would have returned its batch: the batches before it are delivered, the epoch ends there (the
-    readers' outstanding work is cancelled or awaited, whatever they raise) and the next `__iter__` starts a new one.
-    `order` holds the file indices of the epoch in progress."""
+    files have.  The reader threads inflate (PngStaging.decode) into the slots of one ring per kind, of the geometry of the
+    first file (and the first map); per batch and kind there is one copy and one gx_png_unfilter launch."""
 
     def __init__(self, files, batch_size, size=None, crop=None, resize='nearest', map_files=None, label_rule='byte',
                  shuffle=True, seed=0, num_workers=4, device='cuda', depth=4, name='png'):
-        if batch_size <= 0:
-            raise GenesisHipError('%s: batch_size must be positive, not %r' % (name, batch_size))
+        super().__init__(files, batch_size, shuffle, seed, num_workers, device, depth, name)
         if map_files is not None and len(map_files) != len(files):
             raise GenesisHipError('%s: %d map files for %d frames' % (name, len(map_files), len(files)))
         if label_rule not in PLANE_RULES:
             raise GenesisHipError('%s: the label rule must be one of %s, not %r' % (name, sorted(PLANE_RULES), label_rule))
-        self.files = list(files)
         self.map_files = None if map_files is None else list(map_files)
-        self.batch_size = int(batch_size)
         self.size, self.crop, self.resize, self.label_rule = size, crop, resize, label_rule
-        self.shuffle = bool(shuffle)
-        self.rng = np.random.RandomState(int(seed) % (1 << 32))
-        self.workers = max(1, min(int(num_workers), MAX_WORKERS))
-        self.device = torch.device(device)
-        self.depth = max(2, int(depth))
-        self.name = name
-        self.length = -(-len(self.files) // self.batch_size)
-        self.pool = None
-        self.frames = self.maps = None          # _Ring
         self.frame_crop = self.map_crop = None
-        self.copy_stream = None
-        self.ready = [None] * self.depth
-        self.consumed = [None] * self.depth
-        self.jobs = {}                          # batch number -> futures
-        self.order = None
-        self.pending = None                     # (batch number, n) of the batch whose copy is in flight
-        self.submitted = 0
-        self.count = 0
-        self.failed = None                      # a reader's error of the batch after the one just returned
 
-    def __len__(self):
-        return self.length
-
-    @staticmethod
-    def _host_wait(ev):
-        if ev is not None:
-            while not ev.query():
-                time.sleep(2e-4)
-
-    def _read(self, path, staging, i):
+    def _open_ring(self):
+        """-> [the frames' _Ring, the maps' or None]"""
         try:
-            staging.decode(i, read_file(path))
+            g = png_info(read_file(self.files[0])).geometry
+            gm = png_info(read_file(self.map_files[0])).geometry if self.map_files is not None else None
         except (GenesisHipError, OSError) as e:
-            raise GenesisHipError('%s: %s: %s' % (self.name, path, e)) from None
+            raise GenesisHipError('%s: %s' % (self.name, e)) from None
+        box = (lambda q: feeder.centre_box(q[0], q[1], self.crop)) if isinstance(self.crop, int) else (lambda q: self.crop)
+        self.frame_crop, self.map_crop = box(g), (box(gm) if gm is not None else None)
+        return [_Ring(self.depth, self.batch_size, q, self.device) if q is not None else None for q in (g, gm)]
 
-    def _rings(self):
-        """The rings, built from the geometry of the first file (and the first map) the first time a batch is needed."""
-        if self.frames is None:
-            try:
-                g = png_info(read_file(self.files[0])).geometry
-                gm = png_info(read_file(self.map_files[0])).geometry if self.map_files is not None else None
-            except (GenesisHipError, OSError) as e:
-                raise GenesisHipError('%s: %s' % (self.name, e)) from None
-            box = (lambda q: feeder.centre_box(q[0], q[1], self.crop)) if isinstance(self.crop, int) else (lambda q: self.crop)
-            self.frame_crop, self.map_crop = box(g), (box(gm) if gm is not None else None)
-            self.frames = _Ring(self.depth, self.batch_size, g, self.device)
-            self.maps = _Ring(self.depth, self.batch_size, gm, self.device) if gm is not None else None
-            self.copy_stream = torch.cuda.Stream(device=self.device)
-            self.pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix=self.name + '_reader')
-
-    def _submit(self, k):
-        """Hands the files of batch k to the reader threads; they write into slot k % depth."""
-        if k >= self.length:
-            return
-        s = k % self.depth
-        self._host_wait(self.ready[s])                  # the slot's last copy has left the pinned buffer
-        self._host_wait(self.consumed[s])
-        idx = self.order[k * self.batch_size:(k + 1) * self.batch_size]
-        jobs = []
+    def _jobs(self, s, idx):
+        frames, maps = self.ring
         for i, f in enumerate(idx):
-            jobs.append(self.pool.submit(self._read, self.files[f], self.frames.staging[s], i))
-            if self.maps is not None:
-                jobs.append(self.pool.submit(self._read, self.map_files[f], self.maps.staging[s], i))
-        self.jobs[k] = jobs
-        self.submitted = k + 1
+            yield self.files[f], functools.partial(frames.staging[s].decode, i)
+            if maps is not None:
+                yield self.map_files[f], functools.partial(maps.staging[s].decode, i)
 
-    def _copy(self, k):
-        """Waits for the readers of batch k and starts its copy on the side stream."""
-        self.pending = None
-        if k >= self.length:
-            return
-        error = None
-        for j in self.jobs.pop(k):
-            try:
-                j.result()
-            except Exception as e:                      # noqa: BLE001  (whatever a reader raised: the epoch ends either way)
-                error = error or e
-        if error is not None:
-            self._drop()
-            raise error
-        s = k % self.depth
-        n = min(self.batch_size, len(self.files) - k * self.batch_size)
-        with torch.cuda.stream(self.copy_stream):
-            for ring in (self.frames, self.maps):
-                if ring is not None:
-                    ring.dev[s].copy_(ring.staging[s].buffer, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.ready[s] = ev
-        self.pending = (k, n)
+    def _stage(self, s, n, results):
+        for ring in self.ring:
+            if ring is not None:
+                ring.dev[s].copy_(ring.staging[s].buffer, non_blocking=True)
+        return n
 
-    def _drop(self):
-        for jobs in self.jobs.values():
-            for j in jobs:
-                j.cancel()
-        for jobs in self.jobs.values():
-            for j in jobs:
-                if not j.cancelled():
-                    try:
-                        j.result()
-                    except Exception:                   # noqa: BLE001  (the epoch is being dropped)
-                        pass
-        self.jobs = {}
-        self.order = None
-        self.pending = None
-
-    def __iter__(self):
-        if not self.files:
-            raise GenesisHipError('%s: no files' % self.name)
-        self._drop()                                    # an epoch that was left half way
-        self.failed = None
-        self._rings()
-        n = len(self.files)
-        self.order = self.rng.permutation(n) if self.shuffle else np.arange(n)
-        self.count = 0
-        for k in range(self.depth - 1):
-            self._submit(k)
-        self._copy(0)
-        return self
-
-    def __next__(self):
-        if self.failed is not None:
-            e, self.failed = self.failed, None
-            raise e
-        if self.order is None:
-            iter(self)
-        if self.pending is None:
-            self.order = None
-            raise StopIteration
-        k, n = self.pending
-        s = k % self.depth
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(self.ready[s])
-        batch = {'input': decode_staged(self.frames.dev[s], self.batch_size, n, self.frames.geometry, self.size,
-                                        self.frame_crop, self.resize)}
-        if self.maps is not None:
-            batch['instances'] = labels_staged(self.maps.dev[s], self.batch_size, n, self.maps.geometry, self.label_rule,
-                                               self.size, self.map_crop)
-        done = torch.cuda.Event()
-        done.record(cur)
-        self.consumed[s] = done
-        self.count += 1
-        self._submit(k + self.depth - 1)                # keeps the readers depth - 1 batches ahead ...
-        try:
-            self._copy(k + 1)                           # ... and the next batch's copy under the caller's step
-        except Exception as e:                          # noqa: BLE001
-            self.failed = e                             # batch k is good and is returned; the next call raises
+    def _batch(self, s, n):
+        frames, maps = self.ring
+        batch = {'input': decode_staged(frames.dev[s], self.batch_size, n, frames.geometry, self.size, self.frame_crop,
+                                        self.resize)}
+        if maps is not None:
+            batch['instances'] = labels_staged(maps.dev[s], self.batch_size, n, maps.geometry, self.label_rule, self.size,
+                                               self.map_crop)
         return batch
-
-    def close(self):
-        self._drop()
-        if self.pool is not None:
-            self.pool.shutdown(wait=True)
-            self.pool = None
-            self.frames = self.maps = None

@@ -39,7 +39,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import png  # noqa: E402
+from genesis_amd import loading, png  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/shapestacks', 'Path to data folder.')
@@ -91,13 +91,6 @@ def copy_dataset(data_folder, target):
     return target
 
 
-def _shard(shard):
-    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-    if not 0 <= rank < world:
-        raise GenesisHipError('shapestacks: shard must be (rank, world) with 0 <= rank < world, not %r' % (shard,))
-    return rank, world
-
-
 def split_files(cfg, mode, shard=None):
     """(frame files, map files or None) of one split after cfg.shuffle_test and the shard."""
     files = frame_files(cfg.data_folder, cfg.split_name, mode)
@@ -105,7 +98,7 @@ def split_files(cfg, mode, shard=None):
         fprint('shapestacks: test split: %d files permuted once (shuffle_test)' % len(files))
         order = np.random.RandomState(int(getattr(cfg, 'seed', 0)) % (1 << 32)).permutation(len(files))
         files = [files[i] for i in order]
-    rank, world = _shard(shard)
+    rank, world = loading.parse_shard(shard, 'shapestacks')
     files = files[rank::world]
     maps = [map_file(cfg.data_folder, f) for f in files] if cfg.load_instances else None
     return files, maps
@@ -117,7 +110,7 @@ def load(cfg, iseg_labels='reference', shard=None, device='cuda', **unused_kwarg
         raise GenesisHipError('shapestacks: iseg_labels must be one of %s, not %r' % (sorted(ISEG_LABELS), iseg_labels))
     if not os.path.exists(cfg.data_folder):
         raise GenesisHipError('shapestacks: data folder %s does not exist' % cfg.data_folder)
-    fprint('shapestacks: %d reader threads' % min(cfg.num_workers, png.MAX_WORKERS))
+    fprint('shapestacks: %d reader threads' % min(cfg.num_workers, loading.MAX_WORKERS))
 
     if cfg.copy_to_tmp:
         cfg.data_folder = copy_dataset(cfg.data_folder, TMP_FOLDER)

@@ -21,7 +21,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import png  # noqa: E402
+from genesis_amd import loading, png  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/sketchy', 'Path to data folder.')
@@ -71,10 +71,8 @@ def load(cfg, shard=None, device='cuda', **unused_kwargs):
         raise GenesisHipError('sketchy: data folder %s does not exist' % cfg.data_folder)
     if cfg.img_size != IMG_SIZE:                        # the frames are stored at 128 x 128 and are not resized
         raise AssertionError('sketchy: img_size must be %d, not %r' % (IMG_SIZE, cfg.img_size))
-    fprint('sketchy: %d reader threads' % min(cfg.num_workers, png.MAX_WORKERS))
-    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
-    if not 0 <= rank < world:
-        raise GenesisHipError('sketchy: shard must be (rank, world) with 0 <= rank < world, not %r' % (shard,))
+    fprint('sketchy: %d reader threads' % min(cfg.num_workers, loading.MAX_WORKERS))
+    rank, world = loading.parse_shard(shard, 'sketchy')
     loaders = []
     for mode, batch_size, workers in (('train', cfg.batch_size, cfg.num_workers), ('valid', cfg.batch_size, cfg.num_workers),
                                       ('test', 1, 1)):

@@ -11,39 +11,28 @@ import zlib
 import numpy as np
 
 from . import _lib
-from ._lib import GenesisHipError
+from ._lib import GenesisHipError, np_ptr as _ptr
 
 
 class TFRecordError(GenesisHipError):
     """A truncated or corrupt TFRecord stream; the message names the record (0-based index in the file)."""
 
 
-def _ptr(a, offset=0):
-    return ctypes.c_void_p(a.ctypes.data + int(offset))
-
-
-def _as_u8(data):
-    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
-        raise GenesisHipError('tfrecord: expected bytes or a contiguous 1-D uint8 array')
-    return a
-
-
 def crc32c(data):
     """CRC-32C (Castagnoli) of bytes / a uint8 array."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'tfrecord')
     return int(_lib.load().gx_crc32c(_ptr(a), a.size))
 
 
 def masked_crc32c(data):
     """TFRecord's masked CRC-32C: ((c >> 15) | (c << 17)) + 0xa282ead8."""
-    a = _as_u8(data)
+    a = _lib.as_u8(data, 'tfrecord')
     return int(_lib.load().gx_crc32c_masked(_ptr(a), a.size))
 
 
 def find_bytes_list(record, name):
     """(offset, length) of the BytesList payload of feature `name` inside one tf.Example `record` (uint8 array / bytes)."""
-    a = _as_u8(record)
+    a = _lib.as_u8(record, 'tfrecord')
     off, length = ctypes.c_longlong(), ctypes.c_longlong()
     _lib.call('gx_tfexample_find_bytes_list', _ptr(a), a.size, name.encode(), ctypes.byref(off), ctypes.byref(length))
     return off.value, length.value
@@ -52,7 +41,7 @@ def find_bytes_list(record, name):
 def unpack_bytes_list(record, name, out):
     """Concatenates the values of bytes_list feature `name` of `record` into `out`, a writable C-contiguous uint8 array
     (any shape); raises unless they total exactly out.size bytes."""
-    a = _as_u8(record)
+    a = _lib.as_u8(record, 'tfrecord')
     if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
         raise GenesisHipError('tfrecord: out must be a writable C-contiguous uint8 array')
     off, length = find_bytes_list(a, name)

@@ -200,6 +200,25 @@ def test_loader_order_short_batch_epochs_and_shard(tmp_path, golden):
     assert loader.files == files[1::2] and len(loader) == 2
     assert torch.equal(torch.cat([b['input'] for b in loader]).cpu(), want[1::2])
     loader.close()
+    # an epoch left half way after one batch: the next one delivers every file once
+    loader = imagefile.ImageFileLoader(files, 4, S, shuffle=False, num_workers=2, max_side=264)
+    assert torch.equal(next(iter(loader))['input'].cpu(), want[:4])
+    order, got = epoch(loader)
+    assert order.tolist() == list(range(11)) and torch.equal(got, want)
+    loader.close()
+    loader = imagefile.ImageFileLoader(files, 4, S, shuffle=True, seed=7, num_workers=2, max_side=264)
+    assert tuple(next(iter(loader))['input'].shape) == (4, 3, S, S)
+    order, got = epoch(loader)
+    assert sorted(order.tolist()) == list(range(11)) and torch.equal(got, want[torch.from_numpy(order)])
+    loader.close()
+    # a ring deeper than the epoch's three batches: all of them, in order, then the end
+    loader = imagefile.ImageFileLoader(files, 4, S, shuffle=False, num_workers=2, max_side=264, depth=8)
+    it = iter(loader)
+    batches = [next(it)['input'] for _ in range(3)]
+    with pytest.raises(StopIteration):
+        next(it)
+    assert [len(b) for b in batches] == [4, 4, 3] and torch.equal(torch.cat(batches).cpu(), want)
+    loader.close()
 
 
 def test_loader_names_the_bad_file_after_the_good_batches(tmp_path, golden):

@@ -221,6 +221,24 @@ def test_shapestacks_loader(tree, golden):
     assert len(next(train)['input']) == 4                            # the next call starts another epoch
     for l in (train, val, test):
         l.close()
+    # in file order, against the one-call path on the same files (each of which is one of the six, bit for bit)
+    files = S.frame_files(tree, 'default', 'train')
+    maps = [S.map_file(tree, f) for f in files]
+    direct = png.decode_png_batch([png.read_file(f) for f in files], crop=BOX)
+    direct_maps = png.decode_png_labels([png.read_file(f) for f in maps], 'index', crop=BOX)
+    assert sorted(want[frame_key(f)] for f in direct) == list(range(6))
+    for depth in (4, 8):                                             # 8: a ring deeper than the epoch's three batches
+        loader = png.PngFileLoader(files, 2, crop=196, map_files=maps, label_rule='index', shuffle=False, num_workers=2,
+                                   depth=depth)
+        assert len(loader) == 3
+        assert torch.equal(next(iter(loader))['input'], direct[:2])  # an epoch left half way after one batch ...
+        it = iter(loader)                                            # ... and the next one: every file once, in order
+        got = [next(it) for _ in range(3)]
+        with pytest.raises(StopIteration):
+            next(it)
+        assert torch.equal(torch.cat([b['input'] for b in got]), direct)
+        assert torch.equal(torch.cat([b['instances'] for b in got]), direct_maps)
+        loader.close()
 
 
 def test_shapestacks_loader_resized_sharded_and_without_instances(tree, golden):
