@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import GenesisHipError
-from .loading import host_wait
+from .loading import SlotEvents
 
 
 def u8hwc_to_f32chw(frames_u8, img_size=None, out=None):
@@ -273,16 +273,8 @@ class DeviceFeeder(object):
     """Iterates fp32 device batches from an iterable of uint8 HWC host batches (numpy arrays or CPU tensors
     [B, H, W, C]).  A ring of `depth` slots (pinned staging buffer + uint8 device buffer); the host->device copy of
     batch i+1 runs on a side stream while batch i is being consumed, and the consumer's stream waits for it with one
-    event (copy -> compute).
-
-    Slot reuse.  TrainStep.step never host-syncs, so the host runs far ahead of the device: the conversion kernel that
-    reads a uint8 slot may still be queued behind many training steps when the ring comes round to that slot again.
-    A slot is therefore refilled only after the HOST has seen both of its events complete -- the copy out of its pinned
-    buffer and the conversion kernel that read its device buffer (`consumed`, recorded on the consumer's stream) -- by
-    polling; nothing on the device waits compute -> copy.  Measured on MI355X / ROCm 7 under HIP-graph replay
-    (tools/feeder_probe.py): a device-side compute -> copy event wait per batch costs 22 % img/s, and a host that blocks
-    on an event fewer than ~30 batches old starves the graph-launch queue (depth 2: 1450 img/s, depth 8: 3700, against
-    6535 resident) -- hence the deep ring: at depth 32 the poll passes immediately in steady state (64x64: 26 MB).
+    event (copy -> compute).  A slot is refilled only after the host has seen both its copy and the conversion kernels
+    that read it complete: loading.SlotEvents, which gives the measurements behind that and behind the deep ring.
 
     Other datasets' transforms: `crop` = (top, left, h, w) (centre_box) and `resize` ('nearest' / 'bilinear') as in
     transform_frames.  Dict batches {'input': uint8 [B,H,W,C], 'instances': int [B,H,W] or [B,1,H,W]} (as the reference's
@@ -310,14 +302,12 @@ class DeviceFeeder(object):
         self.resize = resize
         self.device = torch.device(device)
         self.depth = max(2, int(depth))
-        self.copy_stream = torch.cuda.Stream(device=self.device)
         self.pinned = [None] * self.depth
         self.dev_u8 = [None] * self.depth
         self.pinned_lab = [None] * self.depth   # dict batches with 'instances': the label maps' staging / device buffers
         self.dev_lab = [None] * self.depth
         self.keys = [None] * self.depth      # keys of a dict batch in the slot; None: an array batch
-        self.ready = [None] * self.depth     # copy-stream event: the H2D copy into dev_u8[s] has executed
-        self.consumed = [None] * self.depth  # consumer-stream event: the conversion kernels have read dev_u8[s] / dev_lab[s]
+        self.events = SlotEvents(self.depth, self.device)
         self.filled = [False] * self.depth
         self.head = 0                        # slot the next __next__ consumes
         self.tail = 0                        # slot the next prefetch fills
@@ -362,13 +352,12 @@ class DeviceFeeder(object):
         if t.dtype != torch.uint8 or t.dim() != 4:
             raise GenesisHipError('feeder: host batches must be uint8 [B,H,W,C]')
         s = self.tail
-        host_wait(self.ready[s])       # pinned[s] is free: its previous copy has executed
-        host_wait(self.consumed[s])    # dev_u8[s] is free: the conversion kernel that read it has run
+        self.events.free(s)
         if lab is not None and (self.pinned_lab[s] is None or self.pinned_lab[s].shape != lab.shape
                                 or self.pinned_lab[s].dtype != lab.dtype):
             for q in range(self.depth):      # the label ring likewise, all at once
                 if self.pinned_lab[q] is None or self.pinned_lab[q].shape != lab.shape or self.pinned_lab[q].dtype != lab.dtype:
-                    host_wait(self.ready[q]); host_wait(self.consumed[q])
+                    self.events.free(q)
                     self.pinned_lab[q] = torch.empty(lab.shape, dtype=lab.dtype, pin_memory=True)
                     self.dev_lab[q] = torch.empty(lab.shape, dtype=lab.dtype, device=self.device)
         if self.pinned[s] is None or self.pinned[s].shape != t.shape:
@@ -377,19 +366,16 @@ class DeviceFeeder(object):
             # segment to get ahead again: 1.5 k -> 2.8 k -> 6.1 k img/s over the first 300 steps, measured)
             for q in range(self.depth):
                 if self.pinned[q] is None or self.pinned[q].shape != t.shape:
-                    host_wait(self.ready[q]); host_wait(self.consumed[q])
+                    self.events.free(q)
                     self.pinned[q] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
                     self.dev_u8[q] = torch.empty(t.shape, dtype=torch.uint8, device=self.device)
         self.pinned[s].copy_(t)
         if lab is not None:
             self.pinned_lab[s].copy_(lab)
-        with torch.cuda.stream(self.copy_stream):
+        with self.events.copying(s):
             self.dev_u8[s].copy_(self.pinned[s], non_blocking=True)
             if lab is not None:
                 self.dev_lab[s].copy_(self.pinned_lab[s], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.ready[s] = ev
         self.keys[s] = tuple(nxt) if is_dict else None
         self.filled[s] = True
         self.tail = (s + 1) % self.depth
@@ -408,22 +394,18 @@ class DeviceFeeder(object):
         s = self.head
         if not self.filled[s]:
             raise StopIteration
-        cur = torch.cuda.current_stream()
-        cur.wait_event(self.ready[s])
-        if self.crop is None and self.resize == 'nearest':
-            x = u8hwc_to_f32chw(self.dev_u8[s], self.img_size)
-        else:
-            x = transform_frames(self.dev_u8[s], self.img_size, self.crop, self.resize)
-        if self.keys[s] is not None:
-            x = {'input': x}
-            if 'instances' in self.keys[s]:
-                x['instances'] = transform_labels(self.dev_lab[s], x['input'].shape[2:], self.crop)
-            elif 'masks' in self.keys[s]:
-                x['instances'] = entity_masks_to_labels(self.dev_lab[s], self.background_entities, x['input'].shape[2:],
-                                                        self.crop, self.mask_layout)
-        done = torch.cuda.Event()
-        done.record(cur)
-        self.consumed[s] = done
+        with self.events.reading(s):
+            if self.crop is None and self.resize == 'nearest':
+                x = u8hwc_to_f32chw(self.dev_u8[s], self.img_size)
+            else:
+                x = transform_frames(self.dev_u8[s], self.img_size, self.crop, self.resize)
+            if self.keys[s] is not None:
+                x = {'input': x}
+                if 'instances' in self.keys[s]:
+                    x['instances'] = transform_labels(self.dev_lab[s], x['input'].shape[2:], self.crop)
+                elif 'masks' in self.keys[s]:
+                    x['instances'] = entity_masks_to_labels(self.dev_lab[s], self.background_entities, x['input'].shape[2:],
+                                                            self.crop, self.mask_layout)
         self.filled[s] = False
         self.head = (s + 1) % self.depth
         self._prefetch()          # refills the next free slot while the caller trains on x

@@ -31,6 +31,7 @@ Differences from the reference, on purpose:
   * `load(cfg, shard=(rank, world))` keeps every world-th file of each split, from file `rank`, for one process per GPU.
   * No throughput printout at load time (the reference's loader_throughput consumes 105 batches first)."""
 import ctypes
+import functools
 import os
 import queue
 import threading
@@ -47,7 +48,8 @@ from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import _lib, jpeg, tfrecord  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
-from genesis_amd.loading import MAX_WORKERS, host_wait, parse_shard  # noqa: E402
+from genesis_amd.loading import (END, MAX_WORKERS, Batcher, Outlet, ShufflePool, SlotEvents, parse_shard,  # noqa: E402
+                                 threaded)
 from genesis_amd.tfrecord import TFRecordError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/gqn_datasets', 'Path to data folder.')
@@ -193,32 +195,9 @@ class HostBatches(object):
 
     def _records(self, stop):
         """The merged stream: (coef row, qtab row, index row, geometry) per record, chunks taken round-robin."""
-        END = object()
-        qs = [queue.Queue(maxsize=_QUEUE_CHUNKS) for _ in range(self.workers)]
         halt = threading.Event()                        # set when the merged stream ends, for whatever reason
-
-        def putter(q):
-            def put(item):
-                while not halt.is_set():
-                    try:
-                        q.put(item, timeout=0.1)
-                        return True
-                    except queue.Full:
-                        pass
-                return False
-            return put
-
-        def run(w):
-            put = putter(qs[w])
-            try:
-                self._read_files(w, put)
-                put(END)
-            except BaseException as e:                  # handed to the merger, and from there to the consumer
-                put(e)
-
-        threads = [threading.Thread(target=run, args=(w,), name='gqn_reader_%d' % w, daemon=True) for w in range(self.workers)]
-        for t in threads:
-            t.start()
+        outlets = [Outlet(_QUEUE_CHUNKS, halt) for _ in range(self.workers)]
+        threads = [o.start(functools.partial(self._read_files, w), 'gqn_reader_%d' % w) for w, o in enumerate(outlets)]
         try:
             live = list(range(self.workers))
             geometry = None
@@ -229,7 +208,7 @@ class HostBatches(object):
                         if stop.is_set():
                             return
                         try:
-                            item = qs[w].get(timeout=0.1)
+                            item = outlets[w].q.get(timeout=0.1)
                         except queue.Empty:
                             pass
                     if item is END:
@@ -250,89 +229,41 @@ class HostBatches(object):
             for t in threads:
                 t.join()
 
-    def _produce(self, put, stop):
+    def _produce(self, put):
         """Runs the epoch and hands every batch to put(item); put returns False once the consumer has gone."""
-        B = self.batch_size
-        state = {'batch': None, 'n': 0, 'geometry': None}
+        B, N = self.batch_size, self.shuffle_records
+        coef = geometry = None                          # of the current record; every record has the same ones
 
-        def emit(coef, qtab, index):
-            if state['batch'] is None:
-                state['batch'] = (np.empty((B, coef.size), dtype=np.int16), np.empty((B, 192), dtype=np.uint16),
-                                  np.empty((B, 3), dtype=np.int64))
-            c, q, ix = state['batch']
-            n = state['n']
-            c[n], q[n], ix[n] = coef, qtab, index
-            state['n'] = n + 1
-            return flush() if state['n'] == B else True
+        def arrays(n):
+            return (np.empty((n, coef.size), dtype=np.int16), np.empty((n, 192), dtype=np.uint16), np.empty((n, 3), dtype=np.int64))
 
-        def flush():
-            c, q, ix = state['batch']
-            n = state['n']
-            state['batch'], state['n'] = None, 0
-            return put({'coef': c[:n], 'qtab': q[:n], 'index': ix[:n], 'geometry': state['geometry']})
+        def emit(*record):
+            dst, n = batch.row()
+            for d, r in zip(dst, record):
+                d[n] = r
+            return batch.written()
 
-        N = self.shuffle_records
-        pool = None
-        fill = 0
-        rng = np.random.RandomState(self.seed) if N > 1 else None
-        for coef, qtab, index, geometry in self._records(stop):
-            state['geometry'] = geometry
-            if N <= 1:
+        batch = Batcher(lambda: arrays(B), B, lambda c, q, ix: {'coef': c, 'qtab': q, 'index': ix, 'geometry': geometry}, put)
+        pool = ShufflePool(N, self.seed) if N > 1 else None
+        rows = None
+        for coef, qtab, index, geometry in self._records(put.halt):
+            if pool is None:
                 if not emit(coef, qtab, index):
                     return
                 continue
-            if pool is None:                            # pages are touched only as rows fill
-                pool = (np.empty((N, coef.size), dtype=np.int16), np.empty((N, 192), dtype=np.uint16),
-                        np.empty((N, 3), dtype=np.int64))
-            if fill < N:
-                j = fill
-                fill += 1
-            else:
-                j = int(rng.randint(N))
-                if not emit(pool[0][j], pool[1][j], pool[2][j]):
-                    return
-            pool[0][j], pool[1][j], pool[2][j] = coef, qtab, index
-        if fill:
-            for j in rng.permutation(fill):             # the stream has ended: drain the pool in random order
-                if not emit(pool[0][j], pool[1][j], pool[2][j]):
-                    return
-        if state['n']:
-            flush()
+            if rows is None:
+                rows = arrays(N)                        # pages are touched only as rows fill
+            j, evict = pool.place()
+            if evict and not emit(*(a[j] for a in rows)):
+                return
+            rows[0][j], rows[1][j], rows[2][j] = coef, qtab, index
+        for j in pool.drain() if pool is not None else ():      # the stream has ended: the pool in random order
+            if not emit(*(a[j] for a in rows)):
+                return
+        batch.flush()
 
     def __iter__(self):
-        q = queue.Queue(maxsize=_QUEUE_BATCHES)
-        stop = threading.Event()
-        END = object()
-
-        def put(item):
-            while not stop.is_set():
-                try:
-                    q.put(item, timeout=0.1)
-                    return True
-                except queue.Full:
-                    pass
-            return False
-
-        def run():
-            try:
-                self._produce(put, stop)
-                put(END)
-            except BaseException as e:                  # handed to the consumer
-                put(e)
-
-        t = threading.Thread(target=run, name='gqn_merger', daemon=True)
-        t.start()
-        try:
-            while True:
-                item = q.get()
-                if item is END:
-                    return
-                if isinstance(item, BaseException):
-                    raise item
-                yield item
-        finally:
-            stop.set()
-            t.join()
+        return threaded(self._produce, 'gqn_merger', _QUEUE_BATCHES)
 
 
 class GQNLoader(object):
@@ -340,8 +271,8 @@ class GQNLoader(object):
     reference's GQNLoader (:87-152): `__len__` = num_frames // batch_size, `__next__` returns {'input': fp32 [B,3,S,S]} and
     raises StopIteration at the end of the epoch; the next `__next__` or `__iter__` starts a new one.
 
-    The ring follows feeder.DeviceFeeder: the copy of batch i + 1 runs on a side stream while batch i is consumed, and a
-    slot is refilled only after the host has seen both its copy and the kernel that read it complete."""
+    The copy of batch i + 1 runs on a side stream while batch i is consumed, and a slot is refilled only after the host has
+    seen both its copy and the kernel that read it complete: loading.SlotEvents, which says why."""
 
     def __init__(self, host_batches, num_frames, img_size, device='cuda', depth=32):
         self.host = host_batches
@@ -353,12 +284,10 @@ class GQNLoader(object):
         self.depth = max(2, int(depth))
         self.count = 0
         self.epoch = None
-        self.copy_stream = None
         self.geometry = None
         self.staging = [None] * self.depth
         self.dev = [None] * self.depth
-        self.ready = [None] * self.depth
-        self.consumed = [None] * self.depth
+        self.events = SlotEvents(self.depth, self.device)
         self.pending = None                 # (slot, n) of the batch whose copy is in flight
         self.slot = 0
 
@@ -371,25 +300,19 @@ class GQNLoader(object):
             b = next(self.epoch)
         except StopIteration:
             return
-        if self.copy_stream is None:
-            self.copy_stream = torch.cuda.Stream(device=self.device)
         if b['geometry'] != self.geometry:              # the whole ring at once, the first time (feeder.py)
             for q in range(self.depth):
-                host_wait(self.ready[q]); host_wait(self.consumed[q])
+                self.events.free(q)
                 self.staging[q] = jpeg.JpegStaging(self.batch_size, *b['geometry'])
                 self.dev[q] = torch.empty(self.staging[q].nbytes, dtype=torch.uint8, device=self.device)
             self.geometry = b['geometry']
         s = self.slot
-        host_wait(self.ready[s])
-        host_wait(self.consumed[s])
+        self.events.free(s)
         n = len(b['coef'])
         self.staging[s].coef[:n] = b['coef']
         self.staging[s].qtab[:n] = b['qtab']
-        with torch.cuda.stream(self.copy_stream):
+        with self.events.copying(s):
             self.dev[s].copy_(self.staging[s].buffer, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.ready[s] = ev
         self.pending = (s, n)
         self.slot = (s + 1) % self.depth
 
@@ -411,12 +334,8 @@ class GQNLoader(object):
             self.epoch = None
             raise StopIteration
         s, n = self.pending
-        cur = torch.cuda.current_stream()
-        cur.wait_event(self.ready[s])
-        x = jpeg.decode_staged(self.dev[s], self.batch_size, n, self.geometry, self.img_size)
-        done = torch.cuda.Event()
-        done.record(cur)
-        self.consumed[s] = done
+        with self.events.reading(s):
+            x = jpeg.decode_staged(self.dev[s], self.batch_size, n, self.geometry, self.img_size)
         self.count += 1
         self._prefetch()                                # fills the next slot while the caller trains on x
         return {'input': x}

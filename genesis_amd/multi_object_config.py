@@ -28,8 +28,6 @@ Differences from the reference, on purpose:
   * No throughput printout at load time (the reference's loader_throughput consumes 105 batches first).
 The pool holds decoded records, as tf.data's does: CLEVR at the defaults is 4096 records of 1.07 MB."""
 import os
-import queue
-import threading
 
 import numpy as np
 import torch
@@ -43,7 +41,7 @@ from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import tfrecord  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
-from genesis_amd.loading import parse_shard  # noqa: E402
+from genesis_amd.loading import Batcher, ShufflePool, parse_shard, threaded  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/multi-object-datasets', 'Path to data folder.')
 flags.DEFINE_string('dataset', 'objects_room', '{multi_dsprites, objects_room, clevr, tetrominoes}')
@@ -130,16 +128,12 @@ class HostBatches(object):
         return (n - self.rank + self.world - 1) // self.world
 
     # ---- reader thread ----
-    def _new_batch(self):
-        B = self.batch_size
-        return (np.empty((B,) + self.image_shape, dtype=np.uint8), np.empty((B,) + self.mask_shape, dtype=np.uint8),
-                np.empty(B, dtype=np.int64))
-
     def _produce(self, put):
         """Runs the epoch and hands every batch to put(item); put returns False once the consumer has gone."""
         B, nb_img = self.batch_size, self.image_bytes
-        rec_bytes = nb_img + self.mask_bytes
-        state = {'batch': self._new_batch(), 'n': 0}
+        batch = Batcher(lambda: (np.empty((B,) + self.image_shape, dtype=np.uint8), np.empty((B,) + self.mask_shape, dtype=np.uint8),
+                                 np.empty(B, dtype=np.int64)),
+                        B, lambda img, msk, idx: {'input': img, 'masks': msk, 'index': idx}, put)
 
         def unpack(rec, index, img_dst, mask_dst):
             try:
@@ -148,97 +142,45 @@ class HostBatches(object):
             except GenesisHipError as e:
                 raise tfrecord.TFRecordError('%s: record %d: %s' % (self.path, index, e)) from None
 
-        def flush(short=False):
-            img, msk, idx = state['batch']
-            n = state['n']
-            if n == B or (short and n):
-                ok = put({'input': img[:n], 'masks': msk[:n], 'index': idx[:n]})
-                state['batch'], state['n'] = self._new_batch(), 0
-                return ok
-            return True
-
-        def emit_row(row, index):
-            img, msk, idx = state['batch']
-            n = state['n']
-            img[n].reshape(-1)[:] = row[:nb_img]
-            msk[n].reshape(-1)[:] = row[nb_img:]
-            idx[n] = index
-            state['n'] = n + 1
-            return flush()
+        def emit_row(j):
+            (img, msk, idx), n = batch.row()
+            img[n].reshape(-1)[:] = rows[j, :nb_img]
+            msk[n].reshape(-1)[:] = rows[j, nb_img:]
+            idx[n] = rows_idx[j]
+            return batch.written()
 
         N = self.shuffle_records
-        pool = pool_idx = rng = None
-        fill = 0
-        if N > 1:
-            rng = np.random.RandomState(self.seed)
+        if N > 1 and self.stop is not None:             # never more rows than the split can fill
+            N = max(2, min(N, (self.stop - self.start + self.world - 1) // self.world))
+        pool = ShufflePool(N, self.seed) if N > 1 else None
+        rows = rows_idx = None
         for index, rec in enumerate(tfrecord.TFRecordReader(self.path, verify_crc=self.verify_crc)):
             if self.stop is not None and index >= self.stop:
                 break
             if index < self.start or (index - self.start) % self.world != self.rank:
                 continue
-            if N <= 1:                                  # file order: unpacked straight into the batch
-                img, msk, idx = state['batch']
-                n = state['n']
+            if pool is None:                            # file order: unpacked straight into the batch
+                (img, msk, idx), n = batch.row()
                 unpack(rec, index, img[n], msk[n])
                 idx[n] = index
-                state['n'] = n + 1
-                if not flush():
+                if not batch.written():
                     return
                 continue
-            if pool is None:
-                if self.stop is not None:               # never more rows than the split can fill
-                    N = max(2, min(N, (self.stop - self.start + self.world - 1) // self.world))
-                pool = np.empty((N, rec_bytes), dtype=np.uint8)     # pages are touched only as rows fill
-                pool_idx = np.empty(N, dtype=np.int64)
-            if fill < N:
-                j = fill
-                fill += 1
-            else:
-                j = int(rng.randint(N))
-                if not emit_row(pool[j], int(pool_idx[j])):
-                    return
-            unpack(rec, index, pool[j, :nb_img], pool[j, nb_img:])
-            pool_idx[j] = index
-        if fill:
-            for j in rng.permutation(fill):             # the stream has ended: drain the pool in random order
-                if not emit_row(pool[j], int(pool_idx[j])):
-                    return
-        flush(short=True)
+            if rows is None:
+                rows = np.empty((N, nb_img + self.mask_bytes), dtype=np.uint8)      # pages are touched only as rows fill
+                rows_idx = np.empty(N, dtype=np.int64)
+            j, evict = pool.place()
+            if evict and not emit_row(j):
+                return
+            unpack(rec, index, rows[j, :nb_img], rows[j, nb_img:])
+            rows_idx[j] = index
+        for j in pool.drain() if pool is not None else ():      # the stream has ended: the pool in random order
+            if not emit_row(j):
+                return
+        batch.flush()
 
     def __iter__(self):
-        q = queue.Queue(maxsize=_QUEUE_BATCHES)
-        stop = threading.Event()
-        END = object()
-
-        def put(item):
-            while not stop.is_set():
-                try:
-                    q.put(item, timeout=0.1)
-                    return True
-                except queue.Full:
-                    pass
-            return False
-
-        def run():
-            try:
-                self._produce(put)
-                put(END)
-            except BaseException as e:                  # handed to the consumer
-                put(e)
-
-        t = threading.Thread(target=run, name='multi_object_reader', daemon=True)
-        t.start()
-        try:
-            while True:
-                item = q.get()
-                if item is END:
-                    return
-                if isinstance(item, BaseException):
-                    raise item
-                yield item
-        finally:
-            stop.set()
-            t.join()
+        return threaded(self._produce, 'multi_object_reader', _QUEUE_BATCHES)
 
 
 class MultiObjectLoader(object):
@@ -255,7 +197,7 @@ class MultiObjectLoader(object):
         self.img_size = int(img_size)
         self.crop, self.size, self.out_size = output_size(host_batches.frame, self.img_size)
         self.device = device
-        if depth is None:       # the feeder's deep ring (feeder.py), capped at 1 GiB of pinned staging for large frames
+        if depth is None:       # the feeder's deep ring (loading.SlotEvents), capped at 1 GiB of pinned staging for large frames
             slot = self.batch_size * (host_batches.image_bytes + host_batches.mask_bytes)
             depth = max(4, min(32, (1 << 30) // slot))
         self.depth = depth

@@ -42,7 +42,7 @@ from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import feeder  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
-from genesis_amd.loading import host_wait, parse_shard  # noqa: E402
+from genesis_amd.loading import SlotEvents, host_wait, parse_shard  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/multi_dsprites/processed', 'Path to data folder.')
 flags.DEFINE_boolean('unique_colours', False, 'Dataset with unique colours.')
@@ -232,13 +232,12 @@ class MultidLoader(object):
 class _StagingRing(object):
     """The host-memmap mode: RING_DEPTH slots of pinned staging + device buffers in the stored dtypes.  The rows of batch
     i + 1 are gathered from the memmap into a pinned slot and copied on a side stream while batch i is consumed; a slot is
-    refilled only after the host has seen its copy and the kernels that read its device buffers complete (feeder.DeviceFeeder
+    refilled only after the host has seen its copy and the kernels that read its device buffers complete (loading.SlotEvents
     explains why the host polls instead of making the copy stream wait for the compute stream)."""
 
     def __init__(self, loader):
         self.loader = loader
         B = loader.batch_size
-        self.copy_stream = torch.cuda.Stream(device=loader.device)
         arrays = [loader.frames] + ([loader.masks] if loader.masks is not None else [])
         self.pinned, self.dev = [], []
         for _ in range(RING_DEPTH):
@@ -246,8 +245,7 @@ class _StagingRing(object):
             self.pinned.append([torch.empty(s, dtype=d, pin_memory=True) for s, d in shapes])
             self.dev.append([torch.empty(s, dtype=d, device=loader.device) for s, d in shapes])
         self.arrays = arrays
-        self.ready = [None] * RING_DEPTH
-        self.consumed = [None] * RING_DEPTH
+        self.events = SlotEvents(RING_DEPTH, loader.device)
         self.staged = {}                 # first row of a staged batch -> its slot
         self.tail = 0
 
@@ -262,28 +260,22 @@ class _StagingRing(object):
         B = min(self.loader.batch_size, n - first)
         rows = self.loader.order[first:first + B]
         s = self.tail
-        host_wait(self.ready[s])
-        host_wait(self.consumed[s])
+        self.events.free(s)
         for a, pin in zip(self.arrays, self.pinned[s]):
             np.take(a, rows, axis=0, out=pin.numpy()[:B])
-        with torch.cuda.stream(self.copy_stream):
+        with self.events.copying(s):
             for pin, dev in zip(self.pinned[s], self.dev[s]):
                 dev[:B].copy_(pin[:B], non_blocking=True)
-            self.ready[s] = torch.cuda.Event()
-            self.ready[s].record(self.copy_stream)
         self.staged[first] = s
         self.tail = (s + 1) % RING_DEPTH
 
     def next(self, first, B, size):
         self._stage(first)
         s = self.staged.pop(first)
-        cur = torch.cuda.current_stream(self.loader.device)
-        cur.wait_event(self.ready[s])
-        batch = {'input': feeder.rows_gather(self.dev[s][0], None, 0, B, size)}
-        if len(self.dev[s]) > 1:
-            batch['instances'] = feeder.rows_gather_labels(self.dev[s][1], None, 0, B, size)
-        self.consumed[s] = torch.cuda.Event()
-        self.consumed[s].record(cur)
+        with self.events.reading(s):
+            batch = {'input': feeder.rows_gather(self.dev[s][0], None, 0, B, size)}
+            if len(self.dev[s]) > 1:
+                batch['instances'] = feeder.rows_gather_labels(self.dev[s][1], None, 0, B, size)
         self._stage(first + B)           # the next batch's rows, while the caller trains on this one
         return batch
 

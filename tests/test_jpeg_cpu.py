@@ -264,8 +264,8 @@ def test_gqn_flags_and_splits_with_no_data_read():
     assert hosts[2].files == ['/nowhere/gqn/rooms_ring_camera/test/1-of-1.tfrecord']
 
 
-def test_gqn_host_stream_without_a_gpu(tmp_path, golden):
-    """The host half end to end: order with one and with several readers, shuffling, frame choice, errors."""
+def write_gqn_files(tmp_path, golden):
+    """3 train files x 5 records x 10 frames of the golden streams -> (paths, {(file, record, frame): case name})."""
     import genesis_amd.gqn_config as Q
     names = MG.GQN_CASES
     root = tmp_path / 'rooms_ring_camera' / 'train'
@@ -279,6 +279,14 @@ def test_gqn_host_stream_without_a_gpu(tmp_path, golden):
             which.update({(fi, r, f): names[k] for f, k in enumerate(ks)})
             records.append(([bytes(golden[names[k] + '_jpeg']) for k in ks], [0.5] * 50))
         MG.write_gqn_tfrecord(path, records)
+    return files, which
+
+
+def test_gqn_host_stream_without_a_gpu(tmp_path, golden):
+    """The host half end to end: order with one and with several readers, shuffling, frame choice, errors."""
+    import genesis_amd.gqn_config as Q
+    names = MG.GQN_CASES
+    files, which = write_gqn_files(tmp_path, golden)
 
     def pixels(b):
         return [R.decode_pixels(c, q, *b['geometry']) for c, q in zip(b['coef'], b['qtab'])]
@@ -306,3 +314,65 @@ def test_gqn_host_stream_without_a_gpu(tmp_path, golden):
     with pytest.raises(tfrecord.TFRecordError, match=r'2-of-3\.tfrecord: record 0: frame 3: .*ends early'):
         list(Q.HostBatches(files, 4, frame=3, num_workers=2))
     assert len(list(Q.HostBatches(files, 4, frame=2, num_workers=2))) == 3
+
+
+def pool_order(stream, N, seed):
+    """The shuffle pool restated on lists: fill N rows without a draw, then one randint(N) per further record (the row it
+    names is emitted and refilled), then one permutation of the filled rows at the end of the stream."""
+    if N <= 1:
+        return list(stream)
+    rng, pool, out = np.random.RandomState(seed), [], []
+    for x in stream:
+        if len(pool) < N:
+            pool.append(x)
+        else:
+            j = int(rng.randint(N))
+            out.append(pool[j])
+            pool[j] = x
+    if pool:
+        out += [pool[j] for j in rng.permutation(len(pool))]
+    return out
+
+
+@pytest.mark.parametrize('workers', [1, 3])
+def test_gqn_shuffled_order_is_the_pools_draw_sequence(tmp_path, golden, workers):
+    """Files of 5 records are one chunk each, so the stream into the pool is in file order with any number of readers."""
+    import genesis_amd.gqn_config as Q
+    files, _ = write_gqn_files(tmp_path, golden)
+    stream = [[fi, r, 3] for fi in range(3) for r in range(5)]
+    for seed in (0, 1):
+        for N in (2, 8, 15, 64):
+            batches = list(Q.HostBatches(files, 4, frame=3, shuffle_records=N, seed=seed, num_workers=workers))
+            assert [len(b['index']) for b in batches] == [4, 4, 4, 3]
+            assert np.concatenate([b['index'] for b in batches]).tolist() == pool_order(stream, N, seed), (seed, N)
+
+
+def gqn_threads():
+    import threading
+    return [t.name for t in threading.enumerate() if t.name == 'gqn_merger' or t.name.startswith('gqn_reader_')]
+
+
+def test_gqn_threads_end_when_the_epoch_is_abandoned_or_fails(tmp_path, golden, monkeypatch):
+    import gc
+    import genesis_amd.gqn_config as Q
+    files, _ = write_gqn_files(tmp_path, golden)
+    monkeypatch.setattr(Q, '_QUEUE_BATCHES', 1)             # 15 batches of 1 behind a queue of 1: the merger blocks on it,
+    monkeypatch.setattr(Q, '_QUEUE_CHUNKS', 1)              # and so do the readers behind the merger
+    monkeypatch.setattr(Q, 'CHUNK_RECORDS', 2)
+    it = iter(Q.HostBatches(files, 1, frame=3, num_workers=3))
+    assert next(it)['index'].tolist() == [[0, 0, 3]]
+    assert 'gqn_merger' in gqn_threads()
+    it.close()
+    assert gqn_threads() == []
+    it = iter(Q.HostBatches(files, 1, frame=3, num_workers=3))
+    next(it)
+    del it                                                  # dropped, not closed
+    gc.collect()
+    assert gqn_threads() == []
+    # a reader's error raised in the consumer: the merger and all three readers have ended when it arrives
+    frames = [bytes(golden[MG.GQN_CASES[0] + '_jpeg'])] * 10
+    frames[3] = frames[3][:200]
+    MG.write_gqn_tfrecord(files[1], [(frames, [0.0] * 50)] * 2)
+    with pytest.raises(tfrecord.TFRecordError, match=r'2-of-3\.tfrecord: record 0: frame 3: .*ends early'):
+        list(Q.HostBatches(files, 1, frame=3, num_workers=3))
+    assert gqn_threads() == []

@@ -177,6 +177,32 @@ def test_shuffle_seed_and_frame_choice(gqn_folder, golden):
     assert other.tolist() != index.tolist()
 
 
+def test_a_ring_of_two_slots_refilled_and_an_abandoned_epoch(gqn_folder):
+    """8 shuffled batches through a ring of depth 2, so every slot is refilled three times: each batch is bit-equal to the
+    host restatement's pixels of the records the host stream's 'index' names.  Then an epoch left after one batch, then a
+    whole one, which equals a fresh loader's."""
+    import genesis_amd.gqn_config as Q
+    sys.path.insert(0, osp.dirname(GOLDEN))
+    import jpeg_restatement as R
+    cfg = make_cfg(gqn_folder, batch_size=2, seed=5)
+    (host, _, _), (frames, _, _) = Q.host_splits(cfg, train_files=TRAIN_FILES, test_files=TEST_FILES, records_per_file=RECORDS)
+    want = [exact_f32(np.stack([R.decode_pixels(c, q, *b['geometry']) for c, q in zip(b['coef'], b['qtab'])])) for b in host]
+    assert [len(w) for w in want] == [2] * 7 + [1]
+    assert np.concatenate([b['index'] for b in host])[:, :2].tolist() != [[fi, r] for fi in range(3) for r in range(RECORDS)]
+
+    def epoch(loader):
+        return [b['input'].cpu() for b in loader]
+
+    loader = Q.GQNLoader(host, frames, cfg.img_size, depth=2)
+    got = epoch(loader)
+    assert len(got) == 8 and all(torch.equal(g, w) for g, w in zip(got, want))
+    assert torch.equal(next(iter(loader))['input'].cpu(), want[0])           # abandoned here, with the second batch staged
+    got = epoch(loader)
+    fresh = epoch(Q.GQNLoader(host, frames, cfg.img_size, depth=2))
+    assert len(got) == len(fresh) == 8 and all(torch.equal(g, f) and torch.equal(g, w) for g, f, w in zip(got, fresh, want))
+    loader.close()
+
+
 def test_train_step_on_a_yielded_batch_has_a_finite_elbo(gqn_folder):
     import genesis_amd.genesisv2_config as G
     from genesis_amd.trainer import TrainStep

@@ -333,3 +333,65 @@ def test_reader_errors_reach_the_consumer_and_the_thread_ends(tmp_path):
     (tng, val, tst), _ = M.host_splits(cfg, val_size=6, test_size=5, shuffle=False)
     with pytest.raises(tfrecord.TFRecordError, match=r'record 0: .*expected 3675'):
         list(tst)
+
+
+def pool_order(stream, N, seed):
+    """The shuffle pool restated on lists: fill N rows without a draw, then one randint(N) per further record (the row it
+    names is emitted and refilled), then one permutation of the filled rows at the end of the stream."""
+    if N <= 1:
+        return list(stream)
+    rng, pool, out = np.random.RandomState(seed), [], []
+    for x in stream:
+        if len(pool) < N:
+            pool.append(x)
+        else:
+            j = int(rng.randint(N))
+            out.append(pool[j])
+            pool[j] = x
+    if pool:
+        out += [pool[j] for j in rng.permutation(len(pool))]
+    return out
+
+
+# (start, stop, shard) and four pool sizes: smaller than the records the split keeps, smaller, equal, larger
+@pytest.mark.parametrize('start, stop, shard, pools', [(5, 11, None, (2, 4, 6, 64)), (11, None, None, (2, 8, 19, 64)),
+                                                       (11, 30, (1, 2), (2, 4, 9, 64))])
+def test_shuffled_order_is_the_pools_draw_sequence(start, stop, shard, pools):
+    import genesis_amd.multi_object_config as M
+    g = np.load(osp.join(GOLDEN, 'multi_object_records.npz'))
+    rank, world = shard or (0, 1)
+    stream = [i for i in range(start, 30 if stop is None else stop) if (i - start) % world == rank]
+    for seed in (0, 1):
+        for N in pools:
+            host = M.HostBatches(fixture_path('objects_room'), (64, 64), 7, 'ehw', start, stop, 4, N, seed, shard)
+            batches, idx = epoch(host)
+            # with `stop` given the pool never has more rows than the split can fill, which sets randint's range
+            rows = N if stop is None else max(2, min(N, -(-(stop - start) // world)))
+            assert idx.tolist() == pool_order(stream, rows, seed), (seed, N)
+            assert [len(b['index']) for b in batches] == [4] * (len(stream) // 4) + [len(stream) % 4] * (len(stream) % 4 > 0)
+            for b in batches:
+                assert np.array_equal(b['input'], g['objects_room_image'][b['index']])
+                assert np.array_equal(b['masks'], g['objects_room_mask'][b['index']])
+
+
+def test_reader_thread_ends_when_the_epoch_is_abandoned(monkeypatch):
+    import gc
+    import threading
+    import genesis_amd.multi_object_config as M
+
+    def readers():
+        return [t for t in threading.enumerate() if t.name == 'multi_object_reader']
+
+    monkeypatch.setattr(M, '_QUEUE_BATCHES', 1)             # 30 batches of 1 behind a queue of 1: the reader blocks on it
+    for shuffle_records in (0, 8):
+        host = M.HostBatches(fixture_path('objects_room'), (64, 64), 7, 'ehw', 0, None, 1, shuffle_records)
+        it = iter(host)
+        next(it)
+        assert len(readers()) == 1
+        it.close()
+        assert not readers()
+        it = iter(host)
+        next(it)
+        del it                                              # dropped, not closed
+        gc.collect()
+        assert not readers()

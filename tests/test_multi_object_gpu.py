@@ -180,6 +180,24 @@ def test_load_yields_the_reference_outputs_of_the_same_records(tmp_path, dataset
     train.close()
 
 
+def test_a_full_epoch_after_an_abandoned_one_equals_an_untouched_loaders(tmp_path):
+    import genesis_amd.multi_object_config as M
+
+    def epoch(loader):
+        batches = [(b['input'].cpu(), b['instances'].cpu()) for b in loader]
+        return torch.cat([x for x, _ in batches]), torch.cat([m for _, m in batches])
+
+    cfg = make_cfg(tmp_path, 'objects_room', seed=3)
+    want_x, want_m = epoch(M.load(cfg, val_size=6, test_size=5)[0])
+    assert want_x.shape == (19, 3, 64, 64) and want_m.shape == (19, 1, 64, 64)
+    train = M.load(cfg, val_size=6, test_size=5)[0]
+    first = next(iter(train))                                # an epoch left after one batch, with the next ones staged
+    assert torch.equal(first['input'].cpu(), want_x[:4])
+    got_x, got_m = epoch(train)
+    assert torch.equal(got_x, want_x) and torch.equal(got_m, want_m)
+    train.close()
+
+
 def test_train_step_on_a_yielded_batch_has_a_finite_elbo(tmp_path):
     import genesis_amd.genesisv2_config as G
     import genesis_amd.multi_object_config as M

@@ -220,6 +220,21 @@ def test_shard_resize_and_no_instances(folder, mem_map):
     check_epoch(train, files['training'][0], None, 32, range(N))
 
 
+def test_mem_map_ring_comes_round_and_survives_an_abandoned_epoch(folder):
+    """13 batches through the RING_DEPTH slots of the host-memmap mode: every slot is refilled; then an epoch left after one
+    batch (with the next one staged), then a whole one."""
+    import genesis_amd.multid_config as M
+    d, files = folder
+    train = M.load(loader_cfg(d, mem_map=True, batch_size=3))[0]
+    assert len(train) == 13 > M.RING_DEPTH
+    check_epoch(train, *files['training'], 64, range(N))
+    half = iter(train)
+    abandoned = half.order.copy()
+    next(half)
+    full = check_epoch(train, *files['training'], 64, range(N))
+    assert full.tolist() != abandoned.tolist()
+
+
 def test_a_loader_batch_through_the_model(folder):
     import genesis_amd.genesisv2_config as G
     import genesis_amd.multid_config as M
