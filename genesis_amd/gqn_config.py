@@ -46,7 +46,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import _lib, jpeg, tfrecord  # noqa: E402
+from genesis_amd import _lib, data_cache, jpeg, tfrecord  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 from genesis_amd.loading import (END, MAX_WORKERS, Batcher, Outlet, ShufflePool, SlotEvents, parse_shard,  # noqa: E402
                                  threaded)
@@ -375,4 +375,6 @@ def load(cfg, frame=None, shard=None, device='cuda', shuffle=True, train_files=T
         raise Exception("Data folder does not exist.")
     fprint(f"Using {min(cfg.num_workers, MAX_WORKERS)} data workers.")
     hosts, sizes = host_splits(cfg, frame, shard, shuffle, train_files, test_files, records_per_file, frames_per_record)
-    return tuple(GQNLoader(h, n, cfg.img_size, device=device) for h, n in zip(hosts, sizes))
+    loaders = tuple(GQNLoader(h, n, cfg.img_size, device=device) for h, n in zip(hosts, sizes))
+    # only the train split goes through the shuffle pool (host_splits)
+    return data_cache.wrap_loaders(cfg, loaders, shuffle=(bool(shuffle), False, False), name='gqn')

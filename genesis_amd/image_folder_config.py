@@ -25,7 +25,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import imagefile, loading  # noqa: E402
+from genesis_amd import data_cache, imagefile, loading  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/images', 'Path to data folder.')
@@ -99,4 +99,4 @@ def load(cfg, shard=None, device='cuda', **unused_kwargs):
         loaders.append(imagefile.ImageFileLoader(files, cfg.batch_size, cfg.img_size, shuffle=True, seed=getattr(cfg, 'seed', 0),
                                                  num_workers=cfg.num_workers, device=device, shard=shard,
                                                  max_side=getattr(cfg, 'max_side', 1024), name='image_folder'))
-    return tuple(loaders)
+    return data_cache.wrap_loaders(cfg, tuple(loaders), name='image_folder')

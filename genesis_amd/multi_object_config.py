@@ -39,7 +39,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import tfrecord  # noqa: E402
+from genesis_amd import data_cache, tfrecord  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 from genesis_amd.loading import Batcher, ShufflePool, parse_shard, threaded  # noqa: E402
 
@@ -294,5 +294,6 @@ def load(cfg, val_size=10000, test_size=10000, shard=None, device='cuda', shuffl
     bg = DATASETS[cfg.dataset]['background_entities']
     world = 1 if shard is None else int(shard[1])
     rank = 0 if shard is None else int(shard[0])
-    return tuple(MultiObjectLoader(h, bg, (n - rank + world - 1) // world, cfg.img_size, device=device)
-                 for h, n in zip(hosts, sizes))
+    loaders = tuple(MultiObjectLoader(h, bg, (n - rank + world - 1) // world, cfg.img_size, device=device)
+                    for h, n in zip(hosts, sizes))
+    return data_cache.wrap_loaders(cfg, loaders, shuffle=bool(shuffle), name='multi_object')

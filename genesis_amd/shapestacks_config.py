@@ -39,7 +39,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import loading, png  # noqa: E402
+from genesis_amd import data_cache, loading, png  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/shapestacks', 'Path to data folder.')
@@ -123,4 +123,4 @@ def load(cfg, iseg_labels='reference', shard=None, device='cuda', **unused_kwarg
                                          resize='bilinear' if size else 'nearest', map_files=maps,
                                          label_rule=ISEG_LABELS[iseg_labels], shuffle=True, seed=getattr(cfg, 'seed', 0),
                                          num_workers=workers, device=device, name='shapestacks'))
-    return tuple(loaders)
+    return data_cache.wrap_loaders(cfg, tuple(loaders), name='shapestacks')

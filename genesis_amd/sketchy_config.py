@@ -21,7 +21,7 @@ _compat.install()
 from forge import flags  # noqa: E402
 from forge.experiment_tools import fprint  # noqa: E402
 
-from genesis_amd import loading, png  # noqa: E402
+from genesis_amd import data_cache, loading, png  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 flags.DEFINE_string('data_folder', 'data/sketchy', 'Path to data folder.')
@@ -79,4 +79,4 @@ def load(cfg, shard=None, device='cuda', **unused_kwargs):
         files = split_files(cfg.data_folder, mode)[rank::world]
         loaders.append(png.PngFileLoader(files, batch_size, shuffle=True, seed=getattr(cfg, 'seed', 0), num_workers=workers,
                                          device=device, name='sketchy'))
-    return tuple(loaders)
+    return data_cache.wrap_loaders(cfg, tuple(loaders), name='sketchy')

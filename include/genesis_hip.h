@@ -1541,6 +1541,34 @@ int gx_u8_resample_ragged_f32chw(const long long* table_host, const long long* t
                                  long long src_bytes, const int* tables, long long tables_values, float* dst, int S_h, int S_w,
                                  gx_stream_t stream);
 
+/* ---- a loader's decoded split kept on the device (genesis_amd/data_cache.py; gx_cache.hip).  The store is planar: frames
+ *      uint8 [rows][C * H * W] in CHW order, labels int16 [rows][H * W]; row_stride is in BYTES, a multiple of 16 and at least
+ *      a row, and the store is 16-byte aligned, so every row starts 16-byte aligned.  Pad bytes between a row's end and the
+ *      next row are never written by a store and never read by a gather.  counters: three int64 device words (8-byte
+ *      aligned) = div_miss, mul_miss, label_misfit; the kernels ADD to them (one atomic per block and non-zero counter), the
+ *      caller zeroes them.
+ *      gx_cache_store_u8: batch fp32 [B, C, H, W] -> rows first_row .. first_row + B (which must not pass capacity_rows) as
+ *      q = clamp(rintf(v * 255.0f), 0, 255), NaN -> 0.  div_miss counts the values whose bits differ from (float)q / 255.0f,
+ *      mul_miss those whose bits differ from (float)q * (1.0f / 255.0f); a NaN, a value outside [0, 1] and -0.0f count as both.
+ *      gx_cache_store_labels_i16: labels int64 [B, 1, H, W] -> (int16)v; label_misfit counts the values outside
+ *      -32768 .. 32767 (they are stored truncated: the count is what tells).  Negative labels survive.
+ *      gx_cache_gather_f32: out fp32 [B, C, H, W] = the rows idx[first .. first + B) of a store of `rows` rows (idx: DEVICE
+ *      vector of idx_len int64 entries; NULL: the rows first .. first + B themselves), each byte q as (float)q / 255.0f
+ *      (GX_CACHE_DIV255) or (float)q * (1.0f / 255.0f) (GX_CACHE_MUL255).  first + B must not pass idx_len (without idx:
+ *      rows); as with gx_rows_gather_f32chw the VALUES of idx are the caller's to check against [0, rows) on the host.
+ *      gx_cache_gather_labels: the same rows of an int16 store -> out int64 [B, 1, H, W], sign-extended.
+ *      B is at most 65535 and a row holds fewer than 2^31 values.  One launch each on `stream`, nothing else. */
+#define GX_CACHE_DIV255 0
+#define GX_CACHE_MUL255 1
+int gx_cache_store_u8(const float* batch, unsigned char* store, long long row_stride, long long first_row,
+                      long long capacity_rows, long long* counters, int B, int C, int H, int W, gx_stream_t stream);
+int gx_cache_store_labels_i16(const long long* labels, short* store, long long row_stride, long long first_row,
+                              long long capacity_rows, long long* counters, int B, int H, int W, gx_stream_t stream);
+int gx_cache_gather_f32(const unsigned char* store, long long row_stride, long long rows, const long long* idx, long long idx_len,
+                        long long first, int mode, float* out, int B, int C, int H, int W, gx_stream_t stream);
+int gx_cache_gather_labels(const short* store, long long row_stride, long long rows, const long long* idx, long long idx_len,
+                           long long first, long long* out, int B, int H, int W, gx_stream_t stream);
+
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
  *      bucket (parameters' gradients + the err / kl tail, genesis_amd/dp.py) is summed IN PLACE over the ranks by one
