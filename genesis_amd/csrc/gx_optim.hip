@@ -5,6 +5,7 @@
 // training step can be replayed from a HIP graph without host round-trips (the reference's
 // `constraint.item()` at geco.py:45 is a device->host sync every iteration).
 #include "gx_common.h"
+#include "gx_philox.h"
 
 namespace {
 
@@ -398,18 +399,6 @@ mse_rmse_kernel(const float* __restrict__ x, const float* __restrict__ r, int B,
 // ---- the step's noise in one launch: counter-based (Philox4x32-10), keyed by (seed, the device-side step counter): a
 //      replayed HIP graph draws fresh numbers every step without the framework's graph-RNG bookkeeping (two offset fills
 //      and one launch per tensor).  Element i of tensor t: counter (i / 4, t, step) -> four 32-bit words.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __global__ void __launch_bounds__(256)
 philox_noise_kernel(float* __restrict__ u, long long nu, float* __restrict__ z, long long nz, unsigned long long seed,
                     const long long* __restrict__ step) {

@@ -21,7 +21,11 @@ What the option changes, on purpose:
 
 Switching it on: `cfg.cache_on_device = True` (an attribute, not a registered flag) or the environment variable
 GENESIS_DATA_CACHE (`1`: the default budget, half of the free device memory; another number: GB per loader) make the data
-configs wrap their three loaders: wrap_loaders()."""
+configs wrap their three loaders: wrap_loaders().
+
+Resident epochs can be augmented on the device (genesis_amd/augment.py): `CachedLoader(loader, augment=Augment(...))` serves
+them through ONE launch of gx_cache_gather_aug per batch instead of the two plain gathers; cfg.augment or GENESIS_AUGMENT
+make wrap_loaders() do that for the train loader."""
 import ctypes
 import os
 import time
@@ -36,6 +40,7 @@ _compat.install()
 from forge.experiment_tools import fprint  # noqa: E402
 
 from genesis_amd import _lib  # noqa: E402
+from genesis_amd import augment as _augment  # noqa: E402
 from genesis_amd._lib import GenesisHipError  # noqa: E402
 
 ENV = 'GENESIS_DATA_CACHE'
@@ -160,9 +165,12 @@ def check_order(order, n):
 class CachedLoader(object):
     """Wraps a loader of device batches {'input': fp32 [B,C,H,W]} (+ 'instances': int64 [B,1,H,W]).  `cache_state` is
     'filling' until the first complete epoch has been stored, then 'resident' or 'off: <reason>'; `order` holds the cache
-    rows of a resident epoch (batch k is rows order[k * B : (k + 1) * B]); `loader` is the wrapped one."""
+    rows of a resident epoch (batch k is rows order[k * B : (k + 1) * B]); `loader` is the wrapped one.  With `augment` (an
+    augment.Augment) the resident epochs are augmented: `epoch` is the counter the random draws are keyed with, 0 in the first
+    resident epoch and one more at every later resident __iter__; set_epoch() sets the next one's when a run is resumed.  The
+    filling epoch and a cache that is off deliver the wrapped loader's batches as they are."""
 
-    def __init__(self, loader, budget_bytes=None, shuffle=None, seed=0, name=None):
+    def __init__(self, loader, budget_bytes=None, shuffle=None, seed=0, name=None, augment=None):
         if not (hasattr(loader, '__len__') and hasattr(loader, 'batch_size')):
             raise GenesisHipError('data_cache: the loader (%s) needs __len__ and batch_size: the store is sized from them'
                                   % type(loader).__name__)
@@ -170,7 +178,12 @@ class CachedLoader(object):
             raise GenesisHipError('data_cache: batch_size must be positive, not %r' % (loader.batch_size,))
         if budget_bytes is not None and not budget_bytes > 0:
             raise GenesisHipError('data_cache: budget_bytes must be positive, not %r' % (budget_bytes,))
+        if augment is not None and not isinstance(augment, _augment.Augment):
+            raise GenesisHipError('data_cache: augment must be an augment.Augment or None, not %r' % (augment,))
         self.loader = loader
+        self.augment = augment
+        self.epoch = 0                     # the resident epoch in progress, from 0: what the augmentation's draws are keyed with
+        self.next_epoch = 0                # ... and the one the next resident __iter__ starts (set_epoch)
         self.batch_size = int(loader.batch_size)
         self.budget_bytes = None if budget_bytes is None else int(budget_bytes)
         self.shuffle = shuffle
@@ -185,6 +198,7 @@ class CachedLoader(object):
         self.shapes = None                 # {key: (shape[1:], dtype)} of the first batch
         self.frames = self.labels = self.counters = self.dev_order = None
         self.pos = 0
+        self.told = False                  # the filling epoch's line about augmentation has been printed
 
     def __len__(self):
         if self.cache_state == 'resident':
@@ -200,6 +214,8 @@ class CachedLoader(object):
             self.order = order
             self.dev_order = torch.from_numpy(order).to(self.frames.device)       # the epoch's one upload
             self.pos = 0
+            self.epoch = self.next_epoch
+            self.next_epoch += 1
             return self
         if self.cache_state == 'filling':
             if self.budget_bytes is None and torch.cuda.is_available():
@@ -208,6 +224,10 @@ class CachedLoader(object):
             if self.counters is not None:
                 self.counters.zero_()
             self.started = time.perf_counter()
+            if self.augment is not None and not self.told:
+                self.told = True
+                fprint('data_cache: %s: the epoch that fills the cache is not augmented; resident epochs are (%r)'
+                       % (self.name, self.augment))
         self.source = iter(self.loader)
         return self
 
@@ -244,6 +264,9 @@ class CachedLoader(object):
         B = min(self.batch_size, self.rows - first)
         self.pos = first + B
         (shape, _) = self.shapes['input']
+        if self.augment is not None:
+            x, y = _augment.gather(self.frames, self.labels, shape, self.augment, self.epoch, self.dev_order, first, B, self.mode)
+            return {'input': x} if y is None else {'input': x, 'instances': y}
         batch = {'input': gather_frames(self.frames, shape, self.dev_order, first, B, self.mode)}
         if self.labels is not None:
             batch['instances'] = gather_labels(self.labels, self.shapes['instances'][0][1:], self.dev_order, first, B)
@@ -288,6 +311,8 @@ class CachedLoader(object):
         y = batch.get('instances')
         if y is not None and (y.dtype != torch.int64 or y.dim() != 4 or y.shape[1] != 1 or y.shape[2:] != x.shape[2:]):
             return 'label maps are %s %s, not int64 [B,1,H,W] of the frames\' size' % (y.dtype, list(y.shape))
+        if self.augment is not None and x.shape[1] > _augment.MAX_CHANNELS:
+            return 'frames of %d channels cannot be augmented (at most %d)' % (x.shape[1], _augment.MAX_CHANNELS)
         capacity = len(self.loader) * self.batch_size
         if capacity <= 0:
             return 'the loader has no batches'
@@ -329,7 +354,14 @@ class CachedLoader(object):
         self.frames = self.labels = self.counters = self.dev_order = None
         self.shapes = None
         self.rows = 0
-        fprint('data_cache: %s: not cached, batches pass through: %s' % (self.name, reason))
+        fprint('data_cache: %s: not cached, batches pass through%s: %s'
+               % (self.name, '' if self.augment is None else ', augmentation is off too', reason))
+
+    def set_epoch(self, n):
+        """The counter of the next resident epoch to start (resuming a run: the number of resident epochs already trained on)."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise GenesisHipError('data_cache: set_epoch takes a non-negative integer, not %r' % (n,))
+        self.epoch = self.next_epoch = n
 
     def close(self):
         """Frees the store and closes the wrapped loader (which becoming resident has done already); iterating again passes
@@ -365,11 +397,15 @@ def requested(cfg):
 
 
 def wrap_loaders(cfg, loaders, shuffle=None, name=None):
-    """The data configs' switch: `loaders` itself unless the cache is requested(), else a tuple of CachedLoaders around
-    them.  shuffle: one value, or one per loader; None follows the loader's own `shuffle` attribute (True without one)."""
+    """The data configs' switch: `loaders` itself unless the cache is requested() or augmentation is (augment.requested: cfg.augment
+    / GENESIS_AUGMENT), else a tuple with CachedLoaders around them.  shuffle: one value, or one per loader; None follows the
+    loader's own `shuffle` attribute (True without one).  Augmentation wraps loader 0 (train), under the same budget rule,
+    whether or not the cache was asked for; the other loaders follow the cache switch alone and are never augmented."""
     on, budget = requested(cfg)
-    if not on:
+    aug = _augment.requested(cfg)
+    if not on and aug is None:
         return loaders
     shuffles = list(shuffle) if isinstance(shuffle, (tuple, list)) else [shuffle] * len(loaders)
-    return tuple(CachedLoader(l, budget, shuffle=s, seed=getattr(cfg, 'seed', 0), name='%s[%d]' % (name, i) if name else None)
+    return tuple(CachedLoader(l, budget, shuffle=s, seed=getattr(cfg, 'seed', 0), name='%s[%d]' % (name, i) if name else None,
+                              augment=aug if i == 0 else None) if on or i == 0 else l
                  for i, (l, s) in enumerate(zip(loaders, shuffles)))

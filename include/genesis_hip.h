@@ -1569,6 +1569,51 @@ int gx_cache_gather_f32(const unsigned char* store, long long row_stride, long l
 int gx_cache_gather_labels(const short* store, long long row_stride, long long rows, const long long* idx, long long idx_len,
                            long long first, long long* out, int B, int H, int W, gx_stream_t stream);
 
+/* ---- augmented batches from the same stores in ONE launch (genesis_amd/augment.py; gx_cache.hip): out fp32 [B, C, H, W] and,
+ *      when labels is not NULL, out_labels int64 [B, 1, H, W] = the rows idx[first .. first + B) of a frame store and of a label
+ *      store of `rows` rows each (strides in bytes, as above), every frame flipped, cropped, resampled back to H x W and scaled
+ *      by a gain, its label map moved by the same geometry.  What follows is the normative text of the transform, "augment v1";
+ *      tests/augment_restatement.py restates it in numpy and the kernel is tested against that bit for bit.
+ *
+ *      Random words.  All of them come from Philox4x32-10 (gx_philox.h).  For the frame of cache row r (the VALUE idx[first + b],
+ *      or first + b without idx: not the position in the batch) in resident epoch e with seed s:
+ *        key = (s & 0xffffffff, s >> 32);  call A: counter (r & 0xffffffff, r >> 32, e & 0xffffffff, 0xA06) -> r0 r1 r2 r3;
+ *        call B: the same counter with last word 0xA07 -> r4 r5 r6 r7.
+ *      t(x) = x >> 8 is a word's 24-bit integer, u(x) = float(t(x)) * 2^-24 (exact) the number in [0, 1).
+ *      Flip.  The frame is mirrored left to right iff t(r0) < flip_t; the host passes flip_t = round(p_flip * 2^24), 0 .. 2^24.
+ *      Scale crop, aspect ratio kept, all in integers with 64-bit products; the host passes wmin = max(1, ceil(min_side * W)):
+ *        w = wmin + ((t(r1) * (W - wmin + 1)) >> 24);       h = clamp((w * H + W / 2) / W, 1, H)   (integer division);
+ *        x0 = (t(r2) * (W - w + 1)) >> 24;                  y0 = (t(r3) * (H - h + 1)) >> 24.
+ *      Resample.  The window [y0, y0 + h) x [x0, x0 + w) is resampled to H x W with half-pixel centres.  For output column x,
+ *      with x' = W - 1 - x when flipped and x' = x otherwise:
+ *        s = (2 * x' + 1) * w - W;   i0 = floor(s / 2W);   rem = s - i0 * 2W;   fx = float(rem) / float(2W), ONE correctly
+ *        rounded fp32 division;   i1 = i0 + 1;   i0 and i1 are then clamped to [0, w - 1].
+ *      Rows likewise with h, H: j0, j1, fy.  With a.. the bytes at window positions (j0, i0), (j0, i1), (j1, i0), (j1, i1) of the
+ *      channel's plane, converted to fp32:
+ *        top = a00 + (a01 - a00) * fx;   bot = a10 + (a11 - a10) * fx;   v = top + (bot - top) * fy
+ *      with EVERY operation rounded to fp32 on its own (no fused multiply-add).  Labels take the nearest value of the same
+ *      window: window column ((2 * x' + 1) * w) / (2W), window row ((2 * y + 1) * h) / (2H), integer divisions.
+ *      Gain.  With brightness b and colour c in [0, 1):  g = 1 + b * (2 * u(r4) - 1);  for channel ch < C (C <= 3):
+ *        g_ch = g * (1 + c * (2 * u(r[5 + ch]) - 1)), that is r5, r6, r7 for channels 0, 1, 2;   v = min(v * g_ch, 255.0f),
+ *      again every operation rounded on its own (2 * u - 1 is exact).  Labels take no gain.
+ *      Conversion, last, by the store's mode exactly as gx_cache_gather_f32: v / 255.0f (GX_CACHE_DIV255) or
+ *      v * (1.0f / 255.0f) (GX_CACHE_MUL255).
+ *      Identities this form gives (the tests lean on them): w == W gives fx == 0 and i0 == x', hence the byte itself; equal taps
+ *      give the tap; g_ch == 1 changes nothing; so flip_t = 0, wmin = W, b = c = 0 reproduce gx_cache_gather_f32 and
+ *      gx_cache_gather_labels bit for bit, and flip_t = 2^24 their mirror images.
+ *
+ *      params_out (may be NULL): int32 [B][8] = (flip, x0, y0, w, h, bits of g_0, bits of g_1, bits of g_2) of every frame of the
+ *      batch, unused gains as the bits of 1.0f.  Refused besides what gx_cache_gather_f32 refuses (same messages; the label store
+ *      is checked like the frame store): labels and out_labels not both NULL or both given, C > 3, H or W above 32767 (the tap
+ *      arithmetic is 32-bit), a negative epoch (only its low 32 bits enter the counter), flip_t outside [0, 2^24], wmin outside
+ *      [1, W], brightness or colour outside [0, 1) or NaN.  As with the plain gathers the VALUES of idx are the caller's to check.
+ *      One launch on `stream`, nothing else: grid (blocks over the plane's quads of four columns, B), the frame's parameters
+ *      computed once per block and shared through LDS. */
+int gx_cache_gather_aug(const unsigned char* frames, long long frame_stride, const short* labels, long long label_stride,
+                        long long rows, const long long* idx, long long idx_len, long long first, int mode,
+                        unsigned long long seed, long long epoch, int flip_t, int wmin, float brightness, float colour, float* out,
+                        long long* out_labels, int* params_out, int B, int C, int H, int W, gx_stream_t stream);
+
 /* ---- the step's one collective without PyTorch (the reference's only multi-GPU mode is nn.DataParallel,
  *      train.py:153-155: replicas gathered on GPU 0 every iteration).  One process per GPU; each rank's flat fp32 gradient
  *      bucket (parameters' gradients + the err / kl tail, genesis_amd/dp.py) is summed IN PLACE over the ranks by one
