@@ -272,8 +272,12 @@ class GenesisV2(nn.Module):
             autostep.arm(self, x if (rand_pixel is None and eps is None and seed_idx is None) else None)      # the unchanged train.py loop: this iteration on TrainStep's launch structure (autostep.py)
         return self._assemble(self._compute(x, rand_pixel, eps, seed_idx))
 
-    def _compute(self, x, rand_pixel=None, eps=None, seed_idx=None):
-        """The tensors of a forward pass (everything that launches kernels): a dict for _assemble."""
+    def _encode(self, x, rand_pixel=None, eps=None, seed_idx=None, posterior_noise=True):
+        """The forward pass up to the posterior -- UNet encoder, the heads and IC-SBP, the pooled slot features, z_head, PosteriorFn
+        -- and nothing after it: the first half of _compute, and all of genesis_amd.segment.encode.  Returns the dict
+        (log_m, log_s, colour, seeds, idx, z, mu, sigma, log_q, dyn_batched, steps); steps: the per-image step counts of
+        dynamic_K, else None.  posterior_noise=False (encode): no eps is drawn and the model's noise source is not asked --
+        PosteriorFn runs on zeros, which mu and sigma do not depend on."""
         B, _, H, W = x.shape
         K, D = self.K_steps, self.feat_dim
         dev = x.device
@@ -281,7 +285,7 @@ class GenesisV2(nn.Module):
         # --- Extract features (F.relu on the ReLU'd UNet output, genesisv2_config.py:115, is the identity)
         enc_feat = fn.UNetEncoderFn.apply(x, self.encoder.num_blocks, 8, *self.encoder.flat_params())
         # --- Predict attention masks
-        if rand_pixel is None and eps is None and getattr(self, 'noise', None) is not None:
+        if posterior_noise and rand_pixel is None and eps is None and getattr(self, 'noise', None) is not None:
             # a training step's noise source (TrainStep: one Philox launch for both tensors, replayable in its HIP graph)
             rand_pixel, eps = self.noise((B, 1, H, W), (K, B, D), dev)
         if rand_pixel is None:
@@ -331,10 +335,18 @@ class GenesisV2(nn.Module):
                                    ln.weight, ln.bias, ln.eps)              # (pooled / mask mass) -> LayerNorm
         # --- Posterior
         if eps is None:
-            eps = torch.randn(K, B, D, device=dev)
+            eps = torch.randn(K, B, D, device=dev) if posterior_noise else torch.zeros(K, B, D, device=dev)
         zh = fn.linear(zh, self.z_head[1].weight, self.z_head[1].bias, 'relu')
         zh = fn.linear(zh, self.z_head[3].weight, self.z_head[3].bias)
         z, mu, sigma, log_q = fn.PosteriorFn.apply(zh, eps)                  # [K,B,D] x3, [K,B]
+        return dict(log_m=log_m, log_s=log_s, colour=colour, seeds=seeds, idx=idx, z=z, mu=mu, sigma=sigma, log_q=log_q,
+                    dyn_batched=dyn_batched, steps=res[5] if self.dynamic_K else None)
+
+    def _compute(self, x, rand_pixel=None, eps=None, seed_idx=None):
+        """The tensors of a forward pass (everything that launches kernels): a dict for _assemble."""
+        e = self._encode(x, rand_pixel, eps, seed_idx)
+        log_m, log_s, colour, seeds, idx = e['log_m'], e['log_s'], e['colour'], e['seeds'], e['idx']
+        z, mu, sigma, log_q, dyn_batched = e['z'], e['mu'], e['sigma'], e['log_q'], e['dyn_batched']
         # --- Decode latents, reconstruction loss
         err, recon, x_r, log_m_r = self._decode(z, x, self.klm_loss and not self.detach_mr_in_klm)
         # --- Component KL (Genesis.mask_latent_loss, models/genesis_config.py:288-343)

@@ -1045,6 +1045,37 @@ int gx_seg_metrics(const float* base, long long plane_stride, long long image_st
                    const long long* instances, int B, int HW, int K, int max_labels, double* rows, double* acc,
                    unsigned long long* state, double* log, long long log_capacity, gx_stream_t stream);
 
+/* ---- per-object tables of an unsupervised segmentation (genesis_amd/objects.py): what a consumer of a label map asks next --
+ *      which slots are present, how large, where, how confident -- for data without ground truth.  ONE launch per batch; integer
+ *      and fp64 work only.  Planes: the K log-mask planes addressed exactly as gx_seg_metrics addresses them -- either
+ *      base != NULL, plane k of image b at base + k plane_stride + b image_stride floats (planes == NULL), or planes = a HOST
+ *      array of K device pointers to image 0 of each plane (base == NULL, plane_stride ignored), image b image_stride floats
+ *      further; every plane is H W contiguous floats.  x: an optional image, fp32 [B, C, H, W], image b at x + b x_image_stride
+ *      floats, each image C H W contiguous floats, 1 <= C <= 4; NULL: no colour sums (C and x_image_stride are then ignored).
+ *        labels  uint8 [B, H W]: argmax_k of the log-masks (ties: lowest k; a NaN ranks above every number and the first one wins,
+ *                as gx_seg_metrics and torch.argmax).
+ *        geom    int64 [B, K, 8], per slot k over the pixels labelled k (column px, row py): area, x_min, y_min, x_max, y_max, sum_x =
+ *                sum px, sum_y = sum py, border = bit 0 if a pixel lies in column 0, bit 1 row 0, bit 2 column W - 1, bit 3 row
+ *                H - 1.  A slot without pixels is (0, W, H, -1, -1, 0, 0, 0).  Bit-exact.
+ *        soft    fp64 [B, K, 6], per slot k: mass = sum over ALL pixels of exp((double)log_m_k), inside = the same sum over the
+ *                pixels labelled k, c0..c3 = sum over the pixels labelled k of (double)x[c] (0 for c >= C, or when x is NULL).
+ *                Every operation after the fp32 load is fp64, each rounded on its own; exp(-inf) = 0, and so is exp(-1e10), the
+ *                padding of dynamic_K.  A NaN log-mask makes its slot's mass NaN (and inside, where it wins the pixel).
+ *      Plan: one workgroup of 256 threads per image and nothing shared between workgroups.  Thread t owns the pixel quads t,
+ *      t + 256, ... (pixels 4q .. 4q + 3) in both passes: pass 1 takes the argmax and writes labels; pass 2 goes slot after slot,
+ *      every thread adding its pixels in ascending order into private accumulators, then a shuffle butterfly over the 64 lanes
+ *      of each wave, then one LDS row per wave, and after the last slot the four rows are added in wave order.  No atomics,
+ *      floating-point or integer.  An image's rows are the same bits whatever batch and batch position it arrives in, and
+ *      whichever load width is used: 16-byte loads of the planes (4-byte of labels) when H W % 4 == 0, every plane of every image
+ *      is 16-byte aligned and labels is 4-byte aligned; 4-byte (1-byte) loads in the same pixel order otherwise.  x is read with
+ *      4-byte loads, every element once.
+ *      GX_EINVAL before any launch: both or neither of base / planes, a null plane, labels, geom or soft; K outside [1, 32];
+ *      B, H or W < 1, H or W > 4096; a negative plane_stride; image_stride below H W; with x non-null, C outside [1, 4] or
+ *      x_image_stride below C H W. */
+int gx_object_table(const float* base, long long plane_stride, long long image_stride, const float* const* planes, const float* x,
+                    long long x_image_stride, int C, int B, int H, int W, int K, unsigned char* labels, long long* geom,
+                    double* soft, gx_stream_t stream);
+
 /* ---- reconstruction quality on the device (genesis_amd/image_quality.py): per image b of pred / target (fp32 [B, C, H, W], image b
  *      at base + b image_stride floats, each image C H W contiguous floats) the row rows[b] = (mse, rmse, psnr, ssim) in fp64 --
  *      every operation from the load onwards is fp64, each rounded on its own (no contraction):
