@@ -638,15 +638,18 @@ def icsbp_fwd(colour, log_sigma, rand_pixel, K, kernel='gaussian', seed_idx=None
     dev = colour.device
     log_m = torch.empty(K, B, 1, H, W, dtype=F32, device=dev)
     log_s = torch.empty(K, B, 1, H, W, dtype=F32, device=dev)
-    seeds = torch.empty(max(K - 1, 0), B, C, dtype=F32, device=dev)
-    idx = torch.empty(max(K - 1, 0), B, dtype=torch.int64, device=dev)
+    # (K = 1 has no step and no seed, but an empty tensor has no address and the entry point refuses a null pointer: one row
+    #  is allocated and an empty slice of it returned)
+    seeds_buf = torch.empty(max(K - 1, 1), B, C, dtype=F32, device=dev)
+    idx_buf = torch.empty(max(K - 1, 1), B, dtype=torch.int64, device=dev)
+    seeds, idx = (seeds_buf, idx_buf) if K > 1 else (seeds_buf[:0], idx_buf[:0])
     if min_mass > 0.0:
         nsteps = torch.empty(B, dtype=torch.int32, device=dev)
         _lib.call('gx_icsbp_fwd_dyn', _p(colour), _p(log_sigma), _p(rand_pixel), _p(seed_idx), B, C, H, W, K,
-                  KERNELS[kernel], float(min_mass), _p(log_m), _p(log_s), _p(seeds), _p(idx), _p(nsteps), _stream())
+                  KERNELS[kernel], float(min_mass), _p(log_m), _p(log_s), _p(seeds_buf), _p(idx_buf), _p(nsteps), _stream())
         return log_m, log_s, seeds, idx, nsteps
     _lib.call('gx_icsbp_fwd', _p(colour), _p(log_sigma), _p(rand_pixel), _p(seed_idx), B, C, H, W, K,
-              KERNELS[kernel], _p(log_m), _p(log_s), _p(seeds), _p(idx), _stream())
+              KERNELS[kernel], _p(log_m), _p(log_s), _p(seeds_buf), _p(idx_buf), _stream())
     return log_m, log_s, seeds, idx
 
 
@@ -659,6 +662,9 @@ def icsbp_bwd(colour, log_sigma, seeds, idx, g_log_m, kernel='gaussian', out_dls
     _chk(dls, 'icsbp_bwd.dls', torch.float64)
     nb = _lib.query('gx_icsbp_bwd_ws_bytes', B, H, W, K)
     ws = _ws(nb, colour.device)
+    if K == 1:      # no step: seeds and idx are empty and have no address; the entry point wants one it will not read
+        seeds = torch.zeros(1, B, C, dtype=F32, device=colour.device)
+        idx = torch.zeros(1, B, dtype=torch.int64, device=colour.device)
     if nsteps is not None:
         _chk(nsteps, 'icsbp_bwd.nsteps', torch.int32)
         _lib.call('gx_icsbp_bwd_dyn', _p(colour), _p(log_sigma), _p(seeds), _p(idx), _p(g_log_m), _p(nsteps), B, C, H, W,

@@ -685,6 +685,38 @@ def _icsbp_bwd(B, C, H, W, K):
                                  _z(max(K - 1, 0), B, dtype=torch.int64), _z(K, B, 1, H, W))
 
 
+def _icsbp_raw(entry, kernel_type=0, min_mass=None, nsteps=True, short=0):
+    """The IC-SBP C entry points with explicit pointers (B = 2, C = 8, 8 x 8, K = 3; zeros of the right sizes): what the wrappers
+    cannot express -- a kernel number outside 0..2, min_mass = 0 or a null nsteps on the dynamic-K entries, a workspace `short`
+    bytes below gx_icsbp_bwd_ws_bytes.  Every one is refused by a GX_CHECK_ARG ahead of the first launch."""
+    import ctypes
+    from genesis_amd import _lib
+    B, C, H, W, K = 2, 8, 8, 8, 3
+
+    def call():
+        p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+        colour, ls, rand, g = _z(B, C, H, W), _z((), dtype=F64), _z(B, 1, H, W), _z(K, B, 1, H, W)
+        log_m, log_s, seeds, idx = _z(K, B, 1, H, W), _z(K, B, 1, H, W), _z(K - 1, B, C), _z(K - 1, B, dtype=torch.int64)
+        ns = p(_z(B, dtype=torch.int32)) if nsteps else None
+        if entry.startswith('gx_icsbp_fwd'):
+            head = (p(colour), p(ls), p(rand), None, B, C, H, W, K, kernel_type)
+            outs = (p(log_m), p(log_s), p(seeds), p(idx))
+            if entry == 'gx_icsbp_fwd_dyn':
+                _lib.call(entry, *head, float(min_mass), *outs, ns, hip._stream())
+            else:
+                _lib.call(entry, *head, *outs, hip._stream())
+            return
+        nb = _lib.query('gx_icsbp_bwd_ws_bytes', B, H, W, K)
+        ws = torch.zeros(nb, dtype=torch.uint8, device=DEV)
+        head = (p(colour), p(ls), p(seeds), p(idx), p(g))
+        tail = (B, C, H, W, K, kernel_type, p(_z(B, C, H, W)), p(_z((), dtype=F64)), p(ws), nb - short, hip._stream())
+        if entry == 'gx_icsbp_bwd_dyn':
+            _lib.call(entry, *head, ns, *tail)
+        else:
+            _lib.call(entry, *head, *tail)
+    return call
+
+
 def _mix(K, std=0.7, B=2, S=4):
     return lambda: hip.mixture_fwd(_z(B, 3, S, S), _z(K * B, 4, S, S), K, std)
 
@@ -732,6 +764,12 @@ REFUSALS = {      # id -> (call, the C entry point its message must name)
     'icsbp_bwd K=18': (_icsbp_bwd(2, 8, 8, 8, 18), 'gx_icsbp_bwd'),
     'icsbp_bwd C=9': (_icsbp_bwd(2, 9, 8, 8, 3), 'gx_icsbp_bwd'),
     'icsbp_bwd HW=96': (_icsbp_bwd(2, 8, 8, 12, 3), 'gx_icsbp_bwd'),
+    'icsbp_fwd_dyn min_mass=0': (_icsbp_raw('gx_icsbp_fwd_dyn', min_mass=0.0), 'gx_icsbp_fwd_dyn'),
+    'icsbp_fwd_dyn nsteps=null': (_icsbp_raw('gx_icsbp_fwd_dyn', min_mass=3.0, nsteps=False), 'gx_icsbp_fwd_dyn'),
+    'icsbp_bwd_dyn nsteps=null': (_icsbp_raw('gx_icsbp_bwd_dyn', nsteps=False), 'gx_icsbp_bwd_dyn'),
+    'icsbp_bwd workspace one byte short': (_icsbp_raw('gx_icsbp_bwd', short=1), 'gx_icsbp_bwd'),
+    'icsbp_fwd kernel_type=3': (_icsbp_raw('gx_icsbp_fwd', kernel_type=3), 'gx_icsbp_fwd'),
+    'icsbp_bwd kernel_type=3': (_icsbp_raw('gx_icsbp_bwd', kernel_type=3), 'gx_icsbp_bwd'),
     'gn_relu_fwd W=6': (_gn_fwd(8, 6), 'gx_gn_relu_fwd'),
     'gn_relu_fwd H=1': (_gn_fwd(1, 8), 'gx_gn_relu_fwd'),
     'gn_relu_fwd C%groups': (_gn_fwd(8, 8, C=6, groups=4), 'gx_gn_relu_fwd'),
