@@ -15,6 +15,7 @@
 // exist.  Backward mirrors this: it gathers the incoming gradient from up to two views.
 #include "gx_common.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -1055,108 +1056,12 @@ gn_relu_bwd_small_kernel(const float* __restrict__ y, const float* __restrict__ 
     }
 }
 
-// gx_gn_last_plan: the record of this thread's last gn_relu_fwd_impl / gn_relu_bwd_impl launch.  Every launcher below fills it
-// on the host, just before it launches, from the values that launch uses (template arguments, grid, block, dynamic LDS, the
-// views' slab counts); nothing reads it on the launch path.  Field order = the GX_GN_PLAN_* indices of include/genesis_hip.h.
-struct GxGnPlan { int kernel, vec, F, UPW, P, threads, grid, lds, CT, keep, wp, chunks, ns0, ns1, ns_in; };
-static_assert(sizeof(GxGnPlan) == GX_GN_PLAN_FIELDS * sizeof(int), "GxGnPlan and GX_GN_PLAN_FIELDS disagree");
-thread_local GxGnPlan t_gn_plan = {};       // kernel GX_GN_NONE until this thread's first launch
-inline void gn_plan_note_fwd(int kernel, bool vec, int F, int UPW, int P, dim3 grid, dim3 block, const InSrc& src) {
-    t_gn_plan = GxGnPlan{kernel, vec ? 1 : 0, F, UPW, P, (int)block.x, (int)grid.x, 0, 0, 0, 0, 0, 0, 0, src.nsplit};
-}
-inline void gn_plan_note_bwd(int kernel, bool vec, int F, int UPW, int P, dim3 grid, dim3 block, size_t lds, int CT, bool keep,
-                             const float* wpart, int chunks, const View& g0, const View& g1) {
-    t_gn_plan = GxGnPlan{kernel, vec ? 1 : 0, F, UPW, P, (int)block.x, (int)grid.x, (int)lds, CT, keep ? 1 : 0, wpart ? 1 : 0,
-                         chunks, g0.nsplit, g1.ptr ? g1.nsplit : 0, 0};
-}
-
 // threads for the tiny-slab kernels, or 0 if the shape does not qualify
 int small_threads(int cpg, int H, int W) {
     const int HW = H * W, m = cpg * HW;
     if (HW >= 256 || (W % 4) != 0 || cpg > 64 || m > 4096) return 0;
     return gx_round_up(m / 4, 64);
 }
-
-// an armed amax link (gx_kq_amax_link) is served when the kernel's first destination is a whole plain tensor (no channel slice, no
-// resampling): one partial maximum of the stored activation per workgroup for the conv that reads it next
-inline float* gn_take_link_out(const float* tensor, int ctot, int c0, int mode, int C, unsigned nwg, size_t covered, bool second_copy = false) {
-    GxAmaxLink& L = gx_amax_link();
-    const bool link_ok = !second_copy && L.parts && !L.tensor && tensor && c0 == 0 && mode == 0 && ctot == C && covered == L.numel;
-    return gx_amax_producer_out(tensor, link_ok, nwg, covered);      // (+ an armed tap, gx_amax_tap: served whatever the destination views are)
-}
-template <int F, int UPW>
-void launch_fwd_reg(dim3 grid, dim3 block, hipStream_t s, const InSrc src, const float* gamma, const float* beta, int C, int H,
-                    int W, int groups, int P, float eps, View d0, View d1, float* mean, float* rstd) {
-    float* ap = d0.ptr ? gn_take_link_out(d0.ptr, d0.ctot, d0.c0, d0.mode, C, grid.x, (size_t)(grid.x / groups) * C * H * W, d1.ptr != nullptr) : nullptr;
-    gn_plan_note_fwd(GX_GN_FWD_REG, true, F, UPW, P, grid, block, src);
-    hipLaunchKernelGGL((gn_relu_fwd_reg_kernel<F, UPW>), grid, block, 0, s, src, gamma, beta, C, H, W, groups, P, eps, d0, d1,
-                       mean, rstd, ap);
-}
-// the two-workgroups-per-CU STAGE kernel serves one unit per wave, 1024 threads and a 4-channel 1x1 conv (RGB + mask logit)
-template <int F, int UPW>
-bool launch_bwd_stage(dim3 grid, dim3 block, hipStream_t s, size_t lds, const float* y, const float* gamma,
-                      const float* beta, const float* mean, const float* rstd, int C, int H, int W, int groups, int P,
-                      View g0, View g1, float* dy, float* part, float* wpart, float* bpart) {
-    if (UPW != 1 || block.x != 1024 || g0.ctot != 4) return false;
-    // an armed amax link (gx_kq_amax_link): one partial maximum of dy per workgroup for the conv that reads dy next
-    float* amax_parts = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)(grid.x / groups) * C * H * W);
-    // slabs of F >= 8 float4 per thread re-read y in the second pass instead of spilling it; smaller ones keep it in registers
-    constexpr bool KEEP = F < 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, true, KEEP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_stage_kernel<F, 4, false, KEEP>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
-#define GX_STAGE_LAUNCH(WP_)                                                                                               \
-    hipLaunchKernelGGL((gn_relu_bwd_stage_kernel<F, 4, WP_, KEEP>), grid, block, lds, s, y, gamma, beta, mean, rstd, C, H, W, \
-                       groups, P, g0, g1, dy, part, wpart, bpart, amax_parts)
-    gn_plan_note_bwd(GX_GN_BWD_STAGE, true, F, UPW, P, grid, block, lds, 4, KEEP, wpart, 0, g0, g1);
-    if (wpart) GX_STAGE_LAUNCH(true); else GX_STAGE_LAUNCH(false);
-#undef GX_STAGE_LAUNCH
-    return true;        // (the record was written above, before the launch)
-}
-
-template <int F, int UPW>
-void launch_bwd_reg(dim3 grid, dim3 block, hipStream_t s, size_t lds, const float* y, const float* gamma, const float* beta,
-                    const float* mean, const float* rstd, int C, int H, int W, int groups, int P, View g0, View g1, float* dy,
-                    float* part, float* wpart, float* bpart) {
-    if (!lds) {
-        float* ap = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)(grid.x / groups) * C * H * W);      // (an armed amax link: dy's partial maxima for its consumer)
-        gn_plan_note_bwd(GX_GN_BWD_REG, true, F, UPW, P, grid, block, 0, 0, false, wpart, 0, g0, g1);
-        hipLaunchKernelGGL((gn_relu_bwd_reg_kernel<F, UPW, false>), grid, block, 0, s, y, gamma, beta, mean, rstd, C, H, W, groups,
-                           P, g0, g1, dy, part, wpart, bpart, ap);
-        return;
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_relu_bwd_reg_kernel<F, UPW, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
-    if (launch_bwd_stage<F, UPW>(grid, block, s, lds, y, gamma, beta, mean, rstd, C, H, W, groups, P, g0, g1, dy, part, wpart, bpart))
-        return;
-    float* ap = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)(grid.x / groups) * C * H * W);
-    gn_plan_note_bwd(GX_GN_BWD_REG_STAGED, true, F, UPW, P, grid, block, lds, 0, false, wpart, 0, g0, g1);
-    hipLaunchKernelGGL((gn_relu_bwd_reg_kernel<F, UPW, true>), grid, block, lds, s, y, gamma, beta, mean, rstd, C, H, W, groups, P,
-                       g0, g1, dy, part, wpart, bpart, ap);
-}
-
-#define GX_GN_REG_DISPATCH(LAUNCH, pl, ...)                                      \
-    do {                                                                         \
-        if (pl.UPW == 1) {                                                       \
-            if (pl.F == 1) LAUNCH<1, 1>(__VA_ARGS__);                            \
-            else if (pl.F == 2) LAUNCH<2, 1>(__VA_ARGS__);                       \
-            else if (pl.F == 4) LAUNCH<4, 1>(__VA_ARGS__);                       \
-            else LAUNCH<8, 1>(__VA_ARGS__);                                      \
-        } else {                                                                 \
-            if (pl.F == 1) LAUNCH<1, 2>(__VA_ARGS__);                            \
-            else if (pl.F == 2) LAUNCH<2, 2>(__VA_ARGS__);                       \
-            else LAUNCH<4, 2>(__VA_ARGS__);                                      \
-        }                                                                        \
-    } while (0)
 
 struct GnRedTable { GxGnRed e[48]; };
 __global__ void __launch_bounds__(256)
@@ -1416,6 +1321,240 @@ gn_relu_active_count_kernel(const float* __restrict__ y, const float* __restrict
     if (threadIdx.x == 0) atomicAdd(count, (unsigned long long)red[0]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host dispatch.  gn_plan_fwd / gn_plan_bwd decide from the shape alone (pure: no thread-local state, no HIP call, no pointer)
+// which kernel runs and with what geometry; gn_relu_fwd_impl / gn_relu_bwd_impl check, plan, take the partial-maxima pointer,
+// note the plan and switch on its kernel, each in one place.  The plan IS the gx_gn_last_plan record (field order = the
+// GX_GN_PLAN_* indices of include/genesis_hip.h): noted on the host just before the launch, read by nothing on the launch path.
+struct GxGnPlan { int kernel, vec, F, UPW, P, threads, grid, lds, CT, keep, wp, chunks, ns0, ns1, ns_in; };
+static_assert(sizeof(GxGnPlan) == GX_GN_PLAN_FIELDS * sizeof(int), "GxGnPlan and GX_GN_PLAN_FIELDS disagree");
+thread_local GxGnPlan t_gn_plan = {};       // kernel GX_GN_NONE until this thread's first launch
+struct GnPlan { GxGnPlan rec; int rc; const char* refusal; };      // rc != GX_OK: refused with this message, rec all zero
+
+constexpr size_t kGnStageLimit = 128 * 1024;    // the largest [Cout][H*W] output gradient the register backward stages in LDS
+constexpr int kGnLdsAttr = 150 * 1024;          // hipFuncAttributeMaxDynamicSharedMemorySize of the kernels that stage it
+
+inline bool gn_shape_ok(int N, int C, int H, int W, int groups) {
+    return N > 0 && C > 0 && groups > 0 && C % groups == 0 && gx_is_pow2(H) && gx_is_pow2(W) && W >= 2 && H >= 2;
+}
+
+// register plan -> tiny slabs -> two-pass (shapes that pass gn_shape_ok)
+GnPlan gn_plan_fwd(int N, int C, int H, int W, int groups, int nsplit_in) {
+    const int cpg = C / groups, m = cpg * H * W, st = small_threads(cpg, H, W);
+    const RegPlan pl = plan_reg(cpg, H, W);
+    GxGnPlan r{};
+    r.vec = 1; r.grid = N * groups; r.ns_in = nsplit_in;
+    if (pl.ok) { r.kernel = GX_GN_FWD_REG; r.F = pl.F; r.UPW = pl.UPW; r.P = pl.P; r.threads = pl.threads; }
+    else if (st) { r.kernel = GX_GN_FWD_SMALL; r.threads = st; }
+    else { r.kernel = GX_GN_FWD_TWOPASS; r.vec = (W % 4) == 0; r.threads = m >= 16384 ? 1024 : (m >= 2048 ? 512 : 256); }
+    return {r, GX_OK, nullptr};
+}
+
+// chunked -> register plan (plain, staged or the stage kernel) -> tiny slabs -> two-pass.  g0_mode 3: gx_gn_relu_bwd_proj's
+// projected source, g0_ctot = Cout; g1_nsplit 0: no second source; want_wpart: only the staging and the chunked kernels serve it
+GnPlan gn_plan_bwd(int N, int C, int H, int W, int groups, int g0_mode, int g0_ctot, int g0_nsplit, int g1_nsplit,
+                   bool want_wpart, size_t ws_bytes) {
+    const int cpg = C / groups, hw = H * W, st = small_threads(cpg, H, W);
+    const RegPlan pl = plan_reg(cpg, H, W);
+    const GnPlan no_wgrad{GxGnPlan{}, GX_EINVAL, "gx_gn_relu_bwd_proj: fused 1x1 weight gradient unsupported for this shape"};
+    GxGnPlan r{};
+    r.vec = 1; r.grid = N * groups; r.wp = want_wpart; r.ns0 = g0_nsplit; r.ns1 = g1_nsplit;
+    if (g0_mode == 3 && !g1_nsplit && proj_split_ok(C, H, W, groups, g0_ctot) &&
+        ws_bytes >= gx_gn_relu_bwd_proj_ws_bytes(N, C, H, W, groups, g0_ctot)) {
+        // slabs beyond one workgroup's registers (128 x 128): chunked sums -> per-slab constants -> chunked apply
+        r.kernel = GX_GN_BWD_SPLIT; r.threads = 256; r.chunks = hw / kSplitPix; r.grid *= r.chunks;
+        r.CT = g0_ctot <= 4 ? 4 : 8;        // the template's output-channel count (rows beyond g0_ctot are idle)
+    }
+    else if (pl.ok) {
+        // projected-gradient source: stage the image's [Cout][H*W] output gradient in LDS when it fits
+        const size_t stage = (g0_mode == 3 && (size_t)g0_ctot * hw * 4 <= kGnStageLimit) ? (size_t)g0_ctot * hw * 4 : 0;
+        if (want_wpart && !stage) return no_wgrad;
+        r.F = pl.F; r.UPW = pl.UPW; r.P = pl.P; r.threads = pl.threads; r.lds = (int)stage;
+        // the two-workgroups-per-CU stage kernel serves one unit per wave, 1024 threads and a 4-channel 1x1 conv (RGB + mask
+        // logit); slabs of F >= 8 float4 per thread re-read y in the second pass instead of spilling it, smaller ones keep it
+        if (!stage) r.kernel = GX_GN_BWD_REG;
+        else if (pl.UPW == 1 && pl.threads == 1024 && g0_ctot == 4) { r.kernel = GX_GN_BWD_STAGE; r.CT = 4; r.keep = pl.F < 8; }
+        else r.kernel = GX_GN_BWD_REG_STAGED;
+    }
+    else if (want_wpart) return no_wgrad;
+    else if (st) { r.kernel = GX_GN_BWD_SMALL; r.threads = st; }
+    else { r.kernel = GX_GN_BWD_TWOPASS; r.vec = (W % 4) == 0; r.threads = hw >= 4096 ? 1024 : (hw >= 1024 ? 256 : 64); }
+    return {r, GX_OK, nullptr};
+}
+
+int gn_plan_copy(const GxGnPlan& p, int* out, int n) {
+    const int* f = reinterpret_cast<const int*>(&p);
+    for (int i = 0; out && i < n && i < GX_GN_PLAN_FIELDS; ++i) out[i] = f[i];
+    return GX_GN_PLAN_FIELDS;
+}
+
+// where a launch of `nwg` workgroups writes one partial maximum of what it stores per workgroup (NULL: nowhere): an armed tap
+// (gx_amax_tap) whatever the destination views are; an armed link (gx_kq_amax_link), for the conv that reads the tensor next, only
+// where `link` allows it and the first destination is a whole plain tensor (no channel slice, no resampling)
+inline float* gn_take_link_out(const float* tensor, int ctot, int c0, int mode, int C, unsigned nwg, size_t covered, bool link) {
+    GxAmaxLink& L = gx_amax_link();
+    const bool link_ok = link && L.parts && !L.tensor && tensor && c0 == 0 && mode == 0 && ctot == C && covered == L.numel;
+    return gx_amax_producer_out(tensor, link_ok, nwg, covered);
+}
+
+inline View make_view(const float* ptr, int ctot, int c0, int mode, int nsplit = 0, size_t sstride = 0) {
+    return View{const_cast<float*>(ptr), ctot, c0, mode, nullptr, 0, nullptr, nsplit, sstride};
+}
+
+// algorithmic bytes of a launch: `passes` whole-tensor reads / writes of `el` elements plus each view once
+inline double gn_prof_bytes(double el, double passes, const View& a, const View& b) {
+    auto vw = [](const View& v) { return !v.ptr ? 0.0 : v.mode == 1 ? 4.0 : (v.mode == 2 ? 0.25 : (v.mode == 3 ? 0.0 : 1.0)); };
+    return 4.0 * el * (passes + vw(a) + vw(b));
+}
+
+// run-time values as template arguments: f(std::true_type / std::false_type), f(GnInt<F>, GnInt<UPW>)
+template <typename Fn>
+void gn_with_bool(bool b, Fn&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int V> using GnInt = std::integral_constant<int, V>;
+#define GX_GN_REG_DISPATCH(LAUNCH, pl)                                           \
+    do {                                                                         \
+        if (pl.UPW == 1) {                                                       \
+            if (pl.F == 1) LAUNCH(GnInt<1>{}, GnInt<1>{});                       \
+            else if (pl.F == 2) LAUNCH(GnInt<2>{}, GnInt<1>{});                  \
+            else if (pl.F == 4) LAUNCH(GnInt<4>{}, GnInt<1>{});                  \
+            else LAUNCH(GnInt<8>{}, GnInt<1>{});                                 \
+        } else {                                                                 \
+            if (pl.F == 1) LAUNCH(GnInt<1>{}, GnInt<2>{});                       \
+            else if (pl.F == 2) LAUNCH(GnInt<2>{}, GnInt<2>{});                  \
+            else LAUNCH(GnInt<4>{}, GnInt<2>{});                                 \
+        }                                                                        \
+    } while (0)
+
+// the kernel, allowed kGnLdsAttr bytes of dynamic LDS at its first use
+template <auto Kernel>
+auto gn_with_lds() {
+    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGnLdsAttr);
+    return (void)once, Kernel;
+}
+
+int gn_relu_fwd_impl(const InSrc& src, const float* gamma, const float* beta, int N, int C, int H, int W, int groups, float eps,
+                     const View& d0, const View& d1, float* mean, float* rstd, gx_stream_t stream) {
+    GX_CHECK_ARG(src.p && gamma && beta && mean && rstd, "gx_gn_relu_fwd: null pointer");
+    GX_CHECK_ARG(d0.ptr || !d1.ptr, "gx_gn_relu_fwd: dst1 without dst0");
+    GX_CHECK_ARG(N > 0 && C > 0 && groups > 0 && C % groups == 0, "gx_gn_relu_fwd: bad N/C/groups");
+    GX_CHECK_ARG(gx_is_pow2(H) && gx_is_pow2(W) && W >= 2 && H >= 2, "gx_gn_relu_fwd: H,W must be powers of two >= 2");
+    int rc = d0.ptr ? check_view("gx_gn_relu_fwd", d0, C) : GX_OK;    // dst0 == NULL: statistics only
+    if (rc) return rc;
+    if (d1.ptr) { rc = check_view("gx_gn_relu_fwd", d1, C); if (rc) return rc; }
+    const GxGnPlan pl = gn_plan_fwd(N, C, H, W, groups, src.nsplit).rec;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(pl.grid), block(pl.threads);
+    const double el = (double)N * C * H * W;
+    // (an armed amax tap and the link are served by the generic kernels too -- the 128 x 128 model's decoder: K B x 8 = 2816 partial
+    //  maxima -- but not by the tiny-slab kernel, where an armed tap stays armed; a second copy rules the link out)
+    float* ap = (pl.kernel != GX_GN_FWD_SMALL && d0.ptr)
+                    ? gn_take_link_out(d0.ptr, d0.ctot, d0.c0, d0.mode, C, grid.x, (size_t)N * C * H * W, !d1.ptr) : nullptr;
+    t_gn_plan = pl;
+    {
+        // algorithmic bytes: read y once, write each destination view once
+        GxProf pf(KID_GN_FWD, s, 8.0 * el, gn_prof_bytes(el, src.nsplit + (src.ysum ? 1.0 : 0.0), d0, d1));
+        switch (pl.kernel) {
+        case GX_GN_FWD_REG: {
+            auto launch = [&](auto F, auto UPW) {
+                hipLaunchKernelGGL((gn_relu_fwd_reg_kernel<decltype(F)::value, decltype(UPW)::value>), grid, block, 0, s, src, gamma,
+                                   beta, C, H, W, groups, pl.P, eps, d0, d1, mean, rstd, ap);
+            };
+            GX_GN_REG_DISPATCH(launch, pl);
+            break;
+        }
+        case GX_GN_FWD_SMALL:
+            hipLaunchKernelGGL(gn_relu_fwd_small_kernel, grid, block, 0, s, src, gamma, beta, C, H, W, groups, eps, d0, d1, mean, rstd);
+            break;
+        case GX_GN_FWD_TWOPASS:
+            gn_with_bool(pl.vec, [&](auto VEC) {
+                hipLaunchKernelGGL(gn_relu_fwd_kernel<decltype(VEC)::value>, grid, block, 0, s, src, gamma, beta, C, H, W, groups, eps,
+                                   d0, d1, mean, rstd, ap);
+            });
+        }
+    }
+    GX_CHECK_LAUNCH("gx_gn_relu_fwd");
+    return GX_OK;
+}
+
+int gn_relu_bwd_impl(const float* y, const float* gamma, const float* beta, const float* mean, const float* rstd, int N, int C,
+                     int H, int W, int groups, const View& g0, const View& g1, float* dy, float* dgamma, float* dbeta,
+                     float* dbias, void* ws, size_t ws_bytes, gx_stream_t stream, float* wpart = nullptr, float* bpart = nullptr) {
+    GX_CHECK_ARG(y && gamma && beta && mean && rstd && dy && dgamma && dbeta && ws, "gx_gn_relu_bwd: null pointer");
+    GX_CHECK_ARG(N > 0 && C > 0 && groups > 0 && C % groups == 0, "gx_gn_relu_bwd: bad N/C/groups");
+    GX_CHECK_ARG(gx_is_pow2(H) && gx_is_pow2(W) && W >= 2 && H >= 2, "gx_gn_relu_bwd: H,W must be powers of two >= 2");
+    GX_CHECK_ARG(ws_bytes >= gx_gn_relu_bwd_ws_bytes(N, C), "gx_gn_relu_bwd: workspace too small");
+    const GnPlan plan = gn_plan_bwd(N, C, H, W, groups, g0.mode, g0.ctot, g0.nsplit, g1.ptr ? g1.nsplit : 0, wpart != nullptr, ws_bytes);
+    if (plan.rc) { gx_set_error("%s", plan.refusal); return plan.rc; }
+    const GxGnPlan& pl = plan.rec;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(pl.grid), block(pl.threads);
+    const int hw = H * W;
+    const double el = (double)N * C * H * W;
+    float* part = (float*)ws;       // [N, C, 3]: the per-image parameter-gradient partials
+    // dy is a whole plain tensor: partial maxima for an armed tap and, except from the two-pass kernel, for the conv that reads
+    // dy next (an armed link); the tiny-slab kernel serves neither (the chunked path: its apply launch writes them)
+    float* ap = pl.kernel == GX_GN_BWD_SMALL
+                    ? nullptr : gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)N * C * H * W, pl.kernel != GX_GN_BWD_TWOPASS);
+    t_gn_plan = pl;
+    {
+        GxProf pf(KID_GN_BWD, s, 16.0 * el, gn_prof_bytes(el, 2.0, g0, g1));
+        // (the register and the stage kernels share one argument list)
+        auto slab = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, pl.lds, s, y, gamma, beta, mean, rstd, C, H, W, groups, pl.P, g0, g1, dy, part,
+                               wpart, bpart, ap);
+        };
+        switch (pl.kernel) {
+        case GX_GN_BWD_SPLIT: {
+            float* rec = part + (size_t)N * C * 3;
+            float* kk = rec + (size_t)N * groups * pl.chunks * kSplitRec;
+            gn_with_bool(pl.CT == 4, [&](auto CT4) {
+                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<(decltype(CT4)::value ? 4 : 8)>, grid, block, 0, s, y, gamma, beta, mean,
+                                   rstd, C, hw, groups, g0, rec);
+            });
+            hipLaunchKernelGGL(gn_bwd_proj_split_combine_kernel, dim3(N * groups), dim3(64), 0, s, (const float*)rec, gamma, rstd, C,
+                               hw, groups, pl.chunks, g0.ctot, kk, part, wpart, bpart);
+            gn_with_bool(pl.CT == 4, [&](auto CT4) {
+                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<(decltype(CT4)::value ? 4 : 8)>, grid, block, 0, s, y, gamma, beta,
+                                   mean, rstd, C, hw, groups, g0, (const float*)kk, dy, ap);
+            });
+            break;
+        }
+        case GX_GN_BWD_REG:
+        case GX_GN_BWD_REG_STAGED:
+        case GX_GN_BWD_STAGE: {
+            auto launch = [&](auto F_, auto UPW_) {
+                constexpr int F = decltype(F_)::value, UPW = decltype(UPW_)::value;
+                if (pl.kernel == GX_GN_BWD_REG) slab(gn_relu_bwd_reg_kernel<F, UPW, false>);
+                else if (pl.kernel == GX_GN_BWD_REG_STAGED) slab(gn_with_lds<gn_relu_bwd_reg_kernel<F, UPW, true>>());
+                else gn_with_bool(pl.wp, [&](auto WP) { slab(gn_with_lds<gn_relu_bwd_stage_kernel<F, 4, decltype(WP)::value, (F < 8)>>()); });
+            };
+            GX_GN_REG_DISPATCH(launch, pl);
+            break;
+        }
+        case GX_GN_BWD_SMALL:
+            hipLaunchKernelGGL(gn_relu_bwd_small_kernel, grid, block, 0, s, y, gamma, beta, mean, rstd, C, H, W, groups, g0, g1, dy, part);
+            break;
+        case GX_GN_BWD_TWOPASS:
+            gn_with_bool(pl.vec, [&](auto VEC) {
+                hipLaunchKernelGGL(gn_relu_bwd_kernel<decltype(VEC)::value>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, H, W,
+                                   groups, g0, g1, dy, part, ap);
+            });
+        }
+    }
+    GX_CHECK_LAUNCH("gx_gn_relu_bwd");
+    if (g_gx_defer_on) {
+        const GxGnRed rec{(const float*)ws, dgamma, dbeta, dbias, N, C};
+        if (gx_defer_push_gn(rec)) return GX_OK;
+        return gx_defer_flush_gn(&rec, 1, s);       // queue full: reduce now, ACCUMULATING like the batched flush
+    }
+    {
+        GxProf pf(KID_GN_PARAM_REDUCE, s, 0.0, 12.0 * N * C);
+        hipLaunchKernelGGL(gn_param_reduce_kernel, dim3(C), dim3(N >= 128 ? 256 : 64), 0, s, (const float*)ws, N, C,
+                           dgamma, dbeta, dbias);
+    }
+    GX_CHECK_LAUNCH("gx_gn_relu_bwd(reduce)");
+    return GX_OK;
+}
 
 }  // namespace
 
@@ -1451,23 +1590,24 @@ int gx_defer_flush_gn(const GxGnRed* items, int n, hipStream_t s) {
 
 extern "C" {
 
-int gx_gn_last_plan(int* out, int n) {
-    const int* f = reinterpret_cast<const int*>(&t_gn_plan);
-    for (int i = 0; out && i < n && i < GX_GN_PLAN_FIELDS; ++i) out[i] = f[i];
-    return GX_GN_PLAN_FIELDS;
-}
+int gx_gn_last_plan(int* out, int n) { return gn_plan_copy(t_gn_plan, out, n); }
 
-static int gn_relu_fwd_impl(const InSrc& src, const float* gamma, const float* beta, int N, int C, int H, int W,
-                            int groups, float eps, float* dst0, int dst0_ctot, int dst0_c0, int dst0_mode,
-                            float* dst1, int dst1_ctot, int dst1_c0, int dst1_mode, float* mean, float* rstd,
-                            gx_stream_t stream);
+// the record the matching launch would note; kernel GX_GN_NONE for arguments the entry points refuse
+int gx_gn_fwd_plan(int N, int C, int H, int W, int groups, int nsplit_in, int* out, int n) {
+    return gn_plan_copy(gn_shape_ok(N, C, H, W, groups) ? gn_plan_fwd(N, C, H, W, groups, nsplit_in).rec : GxGnPlan{}, out, n);
+}
+int gx_gn_bwd_plan(int N, int C, int H, int W, int groups, int g0_mode, int g0_ctot, int g0_nsplit, int g1_nsplit, int want_wpart,
+                   size_t ws_bytes, int* out, int n) {
+    const bool ok = gn_shape_ok(N, C, H, W, groups) && g0_mode >= 0 && g0_mode <= 3 && ws_bytes >= gx_gn_relu_bwd_ws_bytes(N, C);
+    return gn_plan_copy(ok ? gn_plan_bwd(N, C, H, W, groups, g0_mode, g0_ctot, g0_nsplit, g1_nsplit, want_wpart != 0, ws_bytes).rec
+                           : GxGnPlan{}, out, n);
+}
 
 int gx_gn_relu_fwd(const float* y, const float* gamma, const float* beta, int N, int C, int H, int W, int groups,
                    float eps, float* dst0, int dst0_ctot, int dst0_c0, int dst0_mode, float* dst1, int dst1_ctot,
                    int dst1_c0, int dst1_mode, float* mean, float* rstd, gx_stream_t stream) {
-    const InSrc src{y, 1, 0, nullptr, nullptr};
-    return gn_relu_fwd_impl(src, gamma, beta, N, C, H, W, groups, eps, dst0, dst0_ctot, dst0_c0, dst0_mode, dst1,
-                            dst1_ctot, dst1_c0, dst1_mode, mean, rstd, stream);
+    return gx_gn_relu_fwd_parts(y, 1, 0, nullptr, nullptr, gamma, beta, N, C, H, W, groups, eps, dst0, dst0_ctot, dst0_c0, dst0_mode,
+                                dst1, dst1_ctot, dst1_c0, dst1_mode, mean, rstd, stream);      // (a plain tensor: one slab, no bias, no sum)
 }
 
 int gx_gn_relu_fwd_parts(const float* parts, int nsplit, size_t split_stride, const float* conv_bias, float* y_sum,
@@ -1476,59 +1616,9 @@ int gx_gn_relu_fwd_parts(const float* parts, int nsplit, size_t split_stride, co
                          int dst1_c0, int dst1_mode, float* mean, float* rstd, gx_stream_t stream) {
     GX_CHECK_ARG(nsplit >= 1, "gx_gn_relu_fwd_parts: nsplit must be >= 1");
     GX_CHECK_ARG(y_sum || (nsplit == 1 && !conv_bias), "gx_gn_relu_fwd_parts: y_sum is required when summing / biasing");
-    const InSrc src{parts, nsplit, split_stride, conv_bias, y_sum};
-    return gn_relu_fwd_impl(src, gamma, beta, N, C, H, W, groups, eps, dst0, dst0_ctot, dst0_c0, dst0_mode, dst1,
-                            dst1_ctot, dst1_c0, dst1_mode, mean, rstd, stream);
-}
-
-static int gn_relu_fwd_impl(const InSrc& src, const float* gamma, const float* beta, int N, int C, int H, int W,
-                            int groups, float eps, float* dst0, int dst0_ctot, int dst0_c0, int dst0_mode,
-                            float* dst1, int dst1_ctot, int dst1_c0, int dst1_mode, float* mean, float* rstd,
-                            gx_stream_t stream) {
-    const float* y = src.p;
-    GX_CHECK_ARG(y && gamma && beta && mean && rstd, "gx_gn_relu_fwd: null pointer");
-    GX_CHECK_ARG(dst0 || !dst1, "gx_gn_relu_fwd: dst1 without dst0");
-    GX_CHECK_ARG(N > 0 && C > 0 && groups > 0 && C % groups == 0, "gx_gn_relu_fwd: bad N/C/groups");
-    GX_CHECK_ARG(gx_is_pow2(H) && gx_is_pow2(W) && W >= 2 && H >= 2, "gx_gn_relu_fwd: H,W must be powers of two >= 2");
-    View d0{dst0, dst0_ctot, dst0_c0, dst0_mode, nullptr, 0, nullptr},
-         d1{dst1, dst1_ctot, dst1_c0, dst1_mode, nullptr, 0, nullptr};
-    int rc = dst0 ? check_view("gx_gn_relu_fwd", d0, C) : GX_OK;    // dst0 == NULL: statistics only
-    if (rc) return rc;
-    if (dst1) { rc = check_view("gx_gn_relu_fwd", d1, C); if (rc) return rc; }
-    const int m = (C / groups) * H * W;
-    const int threads = m >= 16384 ? 1024 : (m >= 2048 ? 512 : 256);
-    const bool vec = (W % 4) == 0;
-    {
-        // algorithmic bytes: read y once, write each destination view once
-        auto vw = [](int mode) { return mode == 1 ? 4.0 : (mode == 2 ? 0.25 : 1.0); };
-        const double el = (double)N * C * H * W;
-        GxProf pf(KID_GN_FWD, (hipStream_t)stream, 8.0 * el,
-                  4.0 * el * (src.nsplit + (src.ysum ? 1.0 : 0.0) + (dst0 ? vw(dst0_mode) : 0.0) +
-                              (dst1 ? vw(dst1_mode) : 0.0)));
-        const RegPlan pl = plan_reg(C / groups, H, W);
-        const int st = small_threads(C / groups, H, W);
-        if (pl.ok)
-            GX_GN_REG_DISPATCH(launch_fwd_reg, pl, dim3(N * groups), dim3(pl.threads), (hipStream_t)stream, src, gamma,
-                               beta, C, H, W, groups, pl.P, eps, d0, d1, mean, rstd);
-        else if (st) {
-            gn_plan_note_fwd(GX_GN_FWD_SMALL, true, 0, 0, 0, dim3(N * groups), dim3(st), src);
-            hipLaunchKernelGGL(gn_relu_fwd_small_kernel, dim3(N * groups), dim3(st), 0, (hipStream_t)stream, src, gamma,
-                               beta, C, H, W, groups, eps, d0, d1, mean, rstd);
-        } else {
-            // (an armed amax tap and the link are served by the generic kernels too -- the 128 x 128 model's decoder: K B x 8 = 2816
-            //  partial maxima, which every workgroup of the conv that reads them reduces with 16-byte loads)
-            float* ap = dst0 ? gn_take_link_out(dst0, d0.ctot, d0.c0, d0.mode, C, (unsigned)(N * groups), (size_t)N * C * H * W, dst1 != nullptr) : nullptr;
-            gn_plan_note_fwd(GX_GN_FWD_TWOPASS, vec, 0, 0, 0, dim3(N * groups), dim3(threads), src);
-            if (vec)
-                hipLaunchKernelGGL(gn_relu_fwd_kernel<true>, dim3(N * groups), dim3(threads), 0, (hipStream_t)stream, src,
-                                   gamma, beta, C, H, W, groups, eps, d0, d1, mean, rstd, ap);
-            else
-                hipLaunchKernelGGL(gn_relu_fwd_kernel<false>, dim3(N * groups), dim3(threads), 0, (hipStream_t)stream, src,
-                                   gamma, beta, C, H, W, groups, eps, d0, d1, mean, rstd, ap);
-        }
-    }
-    GX_CHECK_LAUNCH("gx_gn_relu_fwd");
-    return GX_OK;
+    return gn_relu_fwd_impl(InSrc{parts, nsplit, split_stride, conv_bias, y_sum}, gamma, beta, N, C, H, W, groups, eps,
+                            make_view(dst0, dst0_ctot, dst0_c0, dst0_mode), make_view(dst1, dst1_ctot, dst1_c0, dst1_mode), mean,
+                            rstd, stream);
 }
 
 size_t gx_gn_relu_bwd_ws_bytes(int N, int C) { return (size_t)N * C * 3 * sizeof(float); }
@@ -1539,11 +1629,6 @@ size_t gx_gn_relu_bwd_proj_ws_bytes(int N, int C, int H, int W, int groups, int 
         b += ((size_t)N * groups * (H * W / kSplitPix) * kSplitRec + (size_t)N * groups * 2) * sizeof(float);
     return b;
 }
-
-static int gn_relu_bwd_impl(const float* y, const float* gamma, const float* beta, const float* mean,
-                            const float* rstd, int N, int C, int H, int W, int groups, const View& v0, const View& v1,
-                            float* dy, float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes,
-                            gx_stream_t stream, float* wpart = nullptr, float* bpart = nullptr);
 
 int gx_gn_relu_bwd(const float* y, const float* gamma, const float* beta, const float* mean, const float* rstd,
                    int N, int C, int H, int W, int groups, const float* g0, int g0_ctot, int g0_c0, int g0_mode,
@@ -1560,13 +1645,12 @@ int gx_gn_relu_bwd_parts(const float* y, const float* gamma, const float* beta, 
                          size_t ws_bytes, gx_stream_t stream) {
     GX_CHECK_ARG(g0, "gx_gn_relu_bwd: null pointer");
     GX_CHECK_ARG(g0_nsplit >= 1 && g1_nsplit >= 1, "gx_gn_relu_bwd_parts: nsplit >= 1");
-    View v0{const_cast<float*>(g0), g0_ctot, g0_c0, g0_mode, nullptr, 0, nullptr, g0_nsplit, g0_split_stride},
-         v1{const_cast<float*>(g1), g1_ctot, g1_c0, g1_mode, nullptr, 0, nullptr, g1_nsplit, g1_split_stride};
+    const View v0 = make_view(g0, g0_ctot, g0_c0, g0_mode, g0_nsplit, g0_split_stride),
+               v1 = make_view(g1, g1_ctot, g1_c0, g1_mode, g1_nsplit, g1_split_stride);
     int rc = check_view("gx_gn_relu_bwd", v0, C);
     if (rc) return rc;
     if (g1) { rc = check_view("gx_gn_relu_bwd", v1, C); if (rc) return rc; }
-    return gn_relu_bwd_impl(y, gamma, beta, mean, rstd, N, C, H, W, groups, v0, v1, dy, dgamma, dbeta, dbias, ws,
-                            ws_bytes, stream);
+    return gn_relu_bwd_impl(y, gamma, beta, mean, rstd, N, C, H, W, groups, v0, v1, dy, dgamma, dbeta, dbias, ws, ws_bytes, stream);
 }
 
 int gx_gn_relu_bwd_proj(const float* y, const float* gamma, const float* beta, const float* mean, const float* rstd,
@@ -1577,105 +1661,18 @@ int gx_gn_relu_bwd_proj(const float* y, const float* gamma, const float* beta, c
     GX_CHECK_ARG((wpart == nullptr) == (bpart == nullptr), "gx_gn_relu_bwd_proj: wpart and bpart go together");
     GX_CHECK_ARG(Cout >= 1 && Cout <= 8, "gx_gn_relu_bwd_proj: Cout must be 1..8 (got %d)", Cout);
     GX_CHECK_ARG((W % 4) == 0 && ((uintptr_t)g_out % 16) == 0, "gx_gn_relu_bwd_proj: W %% 4 == 0 and 16-byte alignment");
-    View v0{const_cast<float*>(g_out), Cout, 0, 3, w, C, gate}, v1{nullptr, 0, 0, 0, nullptr, 0, nullptr};
-    return gn_relu_bwd_impl(y, gamma, beta, mean, rstd, N, C, H, W, groups, v0, v1, dy, dgamma, dbeta, dbias, ws,
-                            ws_bytes, stream, wpart, bpart);
+    View v0 = make_view(g_out, Cout, 0, 3);     // the projected source: the 1x1 conv's weight [Cout, C] and optional gate
+    v0.proj = w; v0.projC = C; v0.pgate = gate;
+    return gn_relu_bwd_impl(y, gamma, beta, mean, rstd, N, C, H, W, groups, v0, make_view(nullptr, 0, 0, 0), dy, dgamma, dbeta,
+                            dbias, ws, ws_bytes, stream, wpart, bpart);
 }
 
-// whether gx_gn_relu_bwd_proj can also produce the 1x1 conv's weight-gradient partials (wpart / bpart)
+// whether gx_gn_relu_bwd_proj can also produce the 1x1 conv's weight-gradient partials (wpart / bpart): its plan is no refusal
 int gx_gn_relu_bwd_proj_fuses_wgrad(int C, int H, int W, int groups, int Cout) {
     if (C <= 0 || groups <= 0 || C % groups || Cout < 1 || Cout > 8 || (C / groups) * Cout > 1024) return 0;
     if (!gx_is_pow2(H) || !gx_is_pow2(W)) return 0;
-    if (proj_split_ok(C, H, W, groups, Cout)) return 1;
-    return plan_reg(C / groups, H, W).ok && (size_t)Cout * H * W * 4 <= 128 * 1024;
+    return gn_plan_bwd(1, C, H, W, groups, 3, Cout, 0, 0, true, gx_gn_relu_bwd_proj_ws_bytes(1, C, H, W, groups, Cout)).rec.kernel != GX_GN_NONE;
 }
-
-static int gn_relu_bwd_impl(const float* y, const float* gamma, const float* beta, const float* mean,
-                            const float* rstd, int N, int C, int H, int W, int groups, const View& v0, const View& v1,
-                            float* dy, float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes,
-                            gx_stream_t stream, float* wpart, float* bpart) {
-    const float* g1 = v1.ptr;
-    const int g0_mode = v0.mode, g1_mode = v1.mode;
-    GX_CHECK_ARG(y && gamma && beta && mean && rstd && dy && dgamma && dbeta && ws,
-                 "gx_gn_relu_bwd: null pointer");
-    GX_CHECK_ARG(N > 0 && C > 0 && groups > 0 && C % groups == 0,
-                 "gx_gn_relu_bwd: bad N/C/groups");
-    GX_CHECK_ARG(gx_is_pow2(H) && gx_is_pow2(W) && W >= 2 && H >= 2, "gx_gn_relu_bwd: H,W must be powers of two >= 2");
-    GX_CHECK_ARG(ws_bytes >= gx_gn_relu_bwd_ws_bytes(N, C), "gx_gn_relu_bwd: workspace too small");
-    const int hw = H * W;
-    const bool vec = (W % 4) == 0;
-    const int threads = hw >= 4096 ? 1024 : (hw >= 1024 ? 256 : 64);
-    hipStream_t s = (hipStream_t)stream;
-    {
-        auto vw = [](int mode) { return mode == 1 ? 4.0 : (mode == 2 ? 0.25 : (mode == 3 ? 0.0 : 1.0)); };
-        const double el = (double)N * C * H * W;
-        GxProf pf(KID_GN_BWD, s, 16.0 * el, 4.0 * el * (2.0 + vw(g0_mode) + (g1 ? vw(g1_mode) : 0.0)));
-        const RegPlan pl = plan_reg(C / groups, H, W);
-        const int st = small_threads(C / groups, H, W);
-        if (v0.mode == 3 && !g1 && proj_split_ok(C, H, W, groups, v0.ctot) &&
-            ws_bytes >= gx_gn_relu_bwd_proj_ws_bytes(N, C, H, W, groups, v0.ctot)) {
-            // slabs beyond one workgroup's registers (128 x 128): chunked sums -> per-slab constants -> chunked apply
-            const int chunks = hw / kSplitPix;
-            float* rec = (float*)ws + (size_t)N * C * 3;
-            float* kk = rec + (size_t)N * groups * chunks * kSplitRec;
-            const dim3 grid(N * groups * chunks), block(256);
-            const int CT = v0.ctot <= 4 ? 4 : 8;      // the template's output-channel count (rows beyond v0.ctot are idle)
-            gn_plan_note_bwd(GX_GN_BWD_SPLIT, true, 0, 0, 0, grid, block, 0, CT, false, wpart, chunks, v0, v1);
-            if (CT == 4)
-                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<4>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
-                                   groups, v0, rec);
-            else
-                hipLaunchKernelGGL(gn_bwd_proj_split_sums_kernel<8>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
-                                   groups, v0, rec);
-            hipLaunchKernelGGL(gn_bwd_proj_split_combine_kernel, dim3(N * groups), dim3(64), 0, s, (const float*)rec, gamma, rstd,
-                               C, hw, groups, chunks, v0.ctot, kk, (float*)ws, wpart, bpart);
-            float* ap = gn_take_link_out(dy, C, 0, 0, C, grid.x, (size_t)N * C * H * W);      // (dy: a whole plain tensor)
-            if (CT == 4)
-                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<4>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
-                                   groups, v0, (const float*)kk, dy, ap);
-            else
-                hipLaunchKernelGGL(gn_bwd_proj_split_apply_kernel<8>, grid, block, 0, s, y, gamma, beta, mean, rstd, C, hw,
-                                   groups, v0, (const float*)kk, dy, ap);
-        }
-        else if (pl.ok) {
-            // projected-gradient source: stage the image's [Cout][H*W] output gradient in LDS when it fits
-            const size_t stage = (v0.mode == 3 && (size_t)v0.ctot * hw * 4 <= 128 * 1024) ? (size_t)v0.ctot * hw * 4 : 0;
-            GX_CHECK_ARG(!wpart || stage, "gx_gn_relu_bwd_proj: fused 1x1 weight gradient unsupported for this shape");
-            GX_GN_REG_DISPATCH(launch_bwd_reg, pl, dim3(N * groups), dim3(pl.threads), s, stage, y, gamma, beta, mean,
-                               rstd, C, H, W, groups, pl.P, v0, v1, dy, (float*)ws, wpart, bpart);
-        }
-        else if (wpart)
-            GX_CHECK_ARG(false, "gx_gn_relu_bwd_proj: fused 1x1 weight gradient unsupported for this shape");
-        else if (st) {
-            gn_plan_note_bwd(GX_GN_BWD_SMALL, true, 0, 0, 0, dim3(N * groups), dim3(st), 0, 0, false, nullptr, 0, v0, v1);
-            hipLaunchKernelGGL(gn_relu_bwd_small_kernel, dim3(N * groups), dim3(st), 0, s, y, gamma, beta, mean, rstd,
-                               C, H, W, groups, v0, v1, dy, (float*)ws);
-        } else {
-            float* ap = gx_amax_producer_out(dy, false, (unsigned)(N * groups), (size_t)N * C * H * W);
-            gn_plan_note_bwd(GX_GN_BWD_TWOPASS, vec, 0, 0, 0, dim3(N * groups), dim3(threads), 0, 0, false, nullptr, 0, v0, v1);
-            if (vec)
-                hipLaunchKernelGGL(gn_relu_bwd_kernel<true>, dim3(N * groups), dim3(threads), 0, s, y, gamma, beta, mean,
-                                   rstd, C, H, W, groups, v0, v1, dy, (float*)ws, ap);
-            else
-                hipLaunchKernelGGL(gn_relu_bwd_kernel<false>, dim3(N * groups), dim3(threads), 0, s, y, gamma, beta, mean,
-                                   rstd, C, H, W, groups, v0, v1, dy, (float*)ws, ap);
-        }
-    }
-    GX_CHECK_LAUNCH("gx_gn_relu_bwd");
-    if (g_gx_defer_on) {
-        const GxGnRed rec{(const float*)ws, dgamma, dbeta, dbias, N, C};
-        if (gx_defer_push_gn(rec)) return GX_OK;
-        return gx_defer_flush_gn(&rec, 1, s);       // queue full: reduce now, ACCUMULATING like the batched flush
-    }
-    {
-        GxProf pf(KID_GN_PARAM_REDUCE, s, 0.0, 12.0 * N * C);
-        hipLaunchKernelGGL(gn_param_reduce_kernel, dim3(C), dim3(N >= 128 ? 256 : 64), 0, s, (const float*)ws, N, C,
-                           dgamma, dbeta, dbias);
-    }
-    GX_CHECK_LAUNCH("gx_gn_relu_bwd(reduce)");
-    return GX_OK;
-}
-
 
 /* gx_gn_relu_active_count: how many elements of relu(gn(y)) are > 0 -- evaluated with the expression every forward / backward
  * kernel of this file (and the normalise-on-load 1x1 conv) uses for its ReLU decision, t = (y - mean) * rstd * gamma + beta, so the

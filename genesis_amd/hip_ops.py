@@ -310,15 +310,33 @@ GN_PLAN_KERNELS = ('none', 'fwd_reg', 'fwd_small', 'fwd_twopass', 'bwd_reg', 'bw
                    'bwd_twopass', 'bwd_split')                                    # GX_GN_NONE ... GX_GN_BWD_SPLIT
 
 
-def gn_last_plan():
-    """The kernel and launch geometry of this thread's last GroupNorm + ReLU forward / backward launch as a dict (kernel by
-    name, the rest integers; kernel 'none' before any launch).  Host state only: needs no GPU and does not synchronise."""
+def _gn_plan(name, *args):
     buf = (ctypes.c_int * len(GN_PLAN_FIELDS))()
-    n = int(_lib.load().gx_gn_last_plan(buf, len(GN_PLAN_FIELDS)))
-    assert n == len(GN_PLAN_FIELDS), 'gx_gn_last_plan has %d fields, hip_ops.GN_PLAN_FIELDS %d' % (n, len(GN_PLAN_FIELDS))
+    n = int(getattr(_lib.load(), name)(*args, buf, len(GN_PLAN_FIELDS)))
+    assert n == len(GN_PLAN_FIELDS), '%s has %d fields, hip_ops.GN_PLAN_FIELDS %d' % (name, n, len(GN_PLAN_FIELDS))
     plan = dict(zip(GN_PLAN_FIELDS, (int(v) for v in buf)))
     plan['kernel'] = GN_PLAN_KERNELS[plan['kernel']]
     return plan
+
+
+def gn_last_plan():
+    """The kernel and launch geometry of this thread's last GroupNorm + ReLU forward / backward launch as a dict (kernel by
+    name, the rest integers; kernel 'none' before any launch).  Host state only: needs no GPU and does not synchronise."""
+    return _gn_plan('gx_gn_last_plan')
+
+
+def gn_fwd_plan(N, C, H, W, groups, nsplit_in=1):
+    """The record a GroupNorm + ReLU forward launch with these arguments would leave in gn_last_plan(); kernel 'none' where the
+    entry point refuses them.  Asks the host dispatch: no launch, no GPU, gn_last_plan() unchanged."""
+    return _gn_plan('gx_gn_fwd_plan', N, C, H, W, groups, nsplit_in)
+
+
+def gn_bwd_plan(N, C, H, W, groups, g0_mode=0, g0_ctot=0, g0_nsplit=1, g1_nsplit=0, want_wpart=False, ws_bytes=None):
+    """... a backward launch.  g1_nsplit 0: no second source; g0_mode 3, g0_ctot = Cout, g0_nsplit 0: gn_relu_bwd_proj's source.
+    ws_bytes None: gx_gn_relu_bwd_ws_bytes(N, C)."""
+    if ws_bytes is None:
+        ws_bytes = _lib.query('gx_gn_relu_bwd_ws_bytes', N, C)
+    return _gn_plan('gx_gn_bwd_plan', N, C, H, W, groups, g0_mode, g0_ctot, g0_nsplit, g1_nsplit, int(bool(want_wpart)), ws_bytes)
 
 
 # ------------------------------------------------------------------ conv3x3

@@ -365,6 +365,15 @@ size_t gx_gn_relu_bwd_proj_ws_bytes(int N, int C, int H, int W, int groups, int 
 #define GX_GN_BWD_TWOPASS 8       /* gn_relu_bwd_kernel<VEC> */
 #define GX_GN_BWD_SPLIT 9         /* gn_bwd_proj_split_sums_kernel<CT> / _combine_kernel / _apply_kernel<CT> */
 int gx_gn_last_plan(int* out, int n);
+/*      gx_gn_fwd_plan / gx_gn_bwd_plan: the same record, as the launch with these arguments WOULD note it -- the host dispatch asked
+ *      directly, no launch, no GPU, the calling thread's gx_gn_last_plan record untouched.  nsplit_in / g0_nsplit / g1_nsplit are the
+ *      slab counts the entry point would be given (gx_gn_relu_fwd: 1; gx_gn_relu_bwd: 1 per source; g1_nsplit 0: no second source).
+ *      g0_mode 3, g0_ctot = Cout, g0_nsplit 0: gx_gn_relu_bwd_proj, want_wpart != 0 with wpart / bpart, ws_bytes its workspace.
+ *      Kernel GX_GN_NONE, every field 0: the entry point refuses these arguments (N / C / groups / H / W, a workspace below
+ *      gx_gn_relu_bwd_ws_bytes, wpart / bpart on a shape that cannot fuse them).  Same out / n / result as gx_gn_last_plan. */
+int gx_gn_fwd_plan(int N, int C, int H, int W, int groups, int nsplit_in, int* out, int n);
+int gx_gn_bwd_plan(int N, int C, int H, int W, int groups, int g0_mode, int g0_ctot, int g0_nsplit, int g1_nsplit, int want_wpart,
+                   size_t ws_bytes, int* out, int n);
 
 /* ---- Instance-Colouring stick-breaking attention: modules/attention.py:162-226.
  *      colour [B,C<=8,H,W]; log_sigma: device pointer to the fp64 0-dim parameter; rand_pixel [B,1,H,W];

@@ -1,6 +1,7 @@
 """The case tables of tests/test_gn_plans_gpu.py against a written enumeration of the kernels and plans the GroupNorm host
 dispatch (genesis_amd/csrc/gx_norm.hip) can pick, the gx_gn_last_plan record before any launch, the input builder's margin
-conditions for every row and the refusals the host decides -- all without a GPU.
+conditions for every row, the refusals the host decides and the dispatch's own answers (gx_gn_fwd_plan / gx_gn_bwd_plan) for
+every row and case -- all without a GPU.
 
 The enumeration is derived from the dispatch (cited per block) and written out here; the tables must cover it, so a deleted or
 re-pointed row fails on the CPU.  mirror_* restate plan_reg / small_threads / proj_split_ok / the thread choices in Python: every
@@ -19,12 +20,12 @@ REG_PAIRS = [(1, 1), (2, 1), (4, 1), (8, 1), (1, 2), (2, 2), (4, 2)]
 REG_P_OF_F8 = [1, 2, 4, 8, 16]                  # <8, 1> is the only pair that runs with P > 1 (P > 1 needs H W > 2048, so F = 8)
 # small_threads: H W < 256, W % 4 == 0, cpg <= 64, m = cpg H W <= 4096 -> round_up(m / 4, 64) threads
 SMALL_THREADS = [64, 256, 1024]
-# gn_relu_fwd_impl: threads = 1024 (m >= 16384), 512 (m >= 2048), 256; gn_relu_bwd_impl: 1024 (H W >= 4096), 256 (>= 1024), 64
+# gn_plan_fwd: threads = 1024 (m >= 16384), 512 (m >= 2048), 256; gn_plan_bwd: 1024 (H W >= 4096), 256 (>= 1024), 64
 TWOPASS_FWD_THREADS = [256, 512, 1024]
 TWOPASS_BWD_THREADS = [64, 256, 1024]
-# launch_bwd_stage: UPW == 1, 1024 threads, Cout == 4 -> gn_relu_bwd_stage_kernel<F, 4, WP, KEEP = F < 8>
+# gn_plan_bwd, a staged register plan: UPW == 1, 1024 threads, Cout == 4 -> gn_relu_bwd_stage_kernel<F, 4, WP, KEEP = F < 8>
 STAGE_CLASSES = [(F, int(F < 8), wp) for F in (1, 2, 4, 8) for wp in (0, 1)]
-# gn_relu_bwd_impl's first branch: CT = 4 (Cout <= 4) or 8
+# gn_plan_bwd's first branch: CT = 4 (Cout <= 4) or 8
 SPLIT_CT = [4, 8]
 # every kernel of gx_gn_last_plan that a backward with a mode-3 source can reach
 PROJ_KERNELS = ['bwd_stage', 'bwd_reg_staged', 'bwd_reg', 'bwd_small', 'bwd_twopass', 'bwd_split']
@@ -262,3 +263,83 @@ def test_fuses_wgrad_query_without_a_gpu():
         ws = _lib.query('gx_gn_relu_bwd_proj_ws_bytes', r['N'], r['cpg'] * r['groups'], r['H'], r['W'], r['groups'], r['Cout'])
         plain = _lib.query('gx_gn_relu_bwd_ws_bytes', r['N'], r['cpg'] * r['groups'])
         assert (ws > plain) == (r['kernel'] == 'bwd_split'), r['id']
+
+
+# ---- the library's own plan (gx_gn_fwd_plan / gx_gn_bwd_plan: the functions the launchers call, asked without a launch)
+def _shape(r):
+    return r['N'], r['cpg'] * r['groups'], r['H'], r['W'], r['groups']
+
+
+def _proj_ws(r):
+    from genesis_amd import _lib
+    return _lib.query('gx_gn_relu_bwd_proj_ws_bytes', *_shape(r), r['Cout'])
+
+
+@pytest.mark.parametrize('r', T.ROWS + T.OFFSET_ROWS + T.VIEW_ROWS, ids=lambda r: r['id'])
+def test_declared_plans_are_the_librarys_plans(r):
+    """What the GPU tests assert of the launch's record holds of the dispatch itself, for every slab count the cases use."""
+    from genesis_amd import hip_ops
+    assert hip_ops.gn_fwd_plan(*_shape(r)) == T.fwd_plan(r)
+    assert hip_ops.gn_bwd_plan(*_shape(r)) == T.bwd_plan(r)
+    if any(q is r for q, _ in T.VIEW_CASES):         # (the second source's mode is not an argument of the plan)
+        assert hip_ops.gn_bwd_plan(*_shape(r), g1_nsplit=1) == T.bwd_plan(r, 1, 1)
+    for ns in sorted({ns for q, ns, _ in T.PART_FWD_CASES if q is r}):
+        assert hip_ops.gn_fwd_plan(*_shape(r), ns) == T.fwd_plan(r, ns)
+    for ns, mode0 in sorted({(ns, m) for q, ns, m in T.PART_BWD_CASES if q is r}):
+        assert hip_ops.gn_bwd_plan(*_shape(r), g0_mode=mode0, g0_nsplit=ns, g1_nsplit=5 - ns) == T.bwd_plan(r, ns, 5 - ns)
+
+
+@pytest.mark.parametrize('r,wp', T.PROJ_CASES, ids=['%s-wp%d' % (r['id'], wp) for r, wp in T.PROJ_CASES])
+def test_declared_projected_plans_are_the_librarys_plans(r, wp):
+    from genesis_amd import hip_ops
+    got = hip_ops.gn_bwd_plan(*_shape(r), g0_mode=3, g0_ctot=r['Cout'], g0_nsplit=0, want_wpart=wp, ws_bytes=_proj_ws(r))
+    assert got == T.proj_plan(r, wp)
+
+
+@pytest.mark.parametrize('r', [r for r in T.PROJ_ROWS if r['kernel'] == 'bwd_split'], ids=lambda r: r['id'])
+def test_a_plain_workspace_falls_through_the_chunked_branch(r):
+    """Pins the last condition of the ladder's first line, `ws_bytes >= gx_gn_relu_bwd_proj_ws_bytes(...)`: with the workspace of
+    gx_gn_relu_bwd_ws_bytes a chunked shape is not refused for its workspace but falls through to the rest of the ladder -- no
+    register plan, so the two-pass kernel, which cannot write wpart / bpart (the third REFUSALS entry)."""
+    from genesis_amd import _lib, hip_ops
+    plain = _lib.query('gx_gn_relu_bwd_ws_bytes', r['N'], r['cpg'] * r['groups'])
+    assert plain < _proj_ws(r)
+    kw = dict(g0_mode=3, g0_ctot=r['Cout'], g0_nsplit=0, ws_bytes=plain)
+    assert hip_ops.gn_bwd_plan(*_shape(r), **kw) == T.plan('bwd_twopass', vec=1, threads=1024, grid=r['N'] * r['groups'])
+    assert hip_ops.gn_bwd_plan(*_shape(r), want_wpart=True, **kw) == T.plan('none')
+    assert hip_ops.gn_bwd_plan(*_shape(r), **dict(kw, ws_bytes=_proj_ws(r) - 4))['kernel'] == 'bwd_twopass'         # 4 bytes short
+    assert hip_ops.gn_bwd_plan(*_shape(r), **dict(kw, ws_bytes=plain - 4)) == T.plan('none')      # below the plain workspace: refused
+
+
+def test_the_queries_agree_with_the_plan_over_a_sweep():
+    """gx_gn_relu_bwd_proj_fuses_wgrad != 0 iff the plan with wpart and the query's workspace is a kernel; the query's workspace
+    exceeds the plain one iff that plan is the chunked path."""
+    from genesis_amd import _lib, hip_ops
+    sizes = [2 ** k for k in range(1, 9)]
+    count, kernels = 0, set()
+    for cpg in (1, 2, 3, 4, 8, 16, 32, 64):
+        for groups in (1, 8):
+            for H in sizes:
+                for W in [w for w in sizes if H * w <= 65536]:
+                    for Cout in range(1, 9):
+                        C = cpg * groups
+                        ws = _lib.query('gx_gn_relu_bwd_proj_ws_bytes', 1, C, H, W, groups, Cout)
+                        plain = _lib.query('gx_gn_relu_bwd_ws_bytes', 1, C)
+                        fuses = _lib.query('gx_gn_relu_bwd_proj_fuses_wgrad', C, H, W, groups, Cout)
+                        kernel = hip_ops.gn_bwd_plan(1, C, H, W, groups, g0_mode=3, g0_ctot=Cout, g0_nsplit=0, want_wpart=True,
+                                                     ws_bytes=ws)['kernel']
+                        assert (fuses != 0) == (kernel != 'none'), (cpg, groups, H, W, Cout, fuses, kernel)
+                        assert (ws > plain) == (kernel == 'bwd_split'), (cpg, groups, H, W, Cout, ws, plain, kernel)
+                        count, kernels = count + 1, kernels | {kernel}
+    assert count == 8 * 2 * 8 * sum(1 for H in sizes for W in sizes if H * W <= 65536)
+    assert kernels == {'none', 'bwd_stage', 'bwd_reg_staged', 'bwd_split'}
+
+
+def test_the_queries_leave_the_record_alone():
+    from genesis_amd import _lib, hip_ops
+    before = hip_ops.gn_last_plan()
+    assert hip_ops.gn_fwd_plan(2, 16, 32, 32, 2)['kernel'] == 'fwd_reg' and hip_ops.gn_bwd_plan(2, 16, 4, 4, 2)['kernel'] == 'bwd_small'
+    _lib.query('gx_gn_relu_bwd_proj_fuses_wgrad', 16, 64, 128, 4, 4)
+    _lib.query('gx_gn_relu_bwd_proj_ws_bytes', 1, 16, 64, 128, 4, 4)
+    assert hip_ops.gn_last_plan() == before
+    assert 'gx_gn_fwd_plan' in _lib.declarations() and 'gx_gn_bwd_plan' in _lib.declarations()

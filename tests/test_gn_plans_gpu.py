@@ -1,8 +1,9 @@
 """GroupNorm + ReLU (genesis_amd/csrc/gx_norm.hip) plan by plan: every kernel family, register plan, thread class and view mode
-the host dispatch (gn_relu_fwd_impl, gn_relu_bwd_impl, plan_reg, small_threads, proj_split_ok) can pick, reached by the smallest
+the host dispatch (gn_plan_fwd, gn_plan_bwd, plan_reg, small_threads, proj_split_ok) can pick, reached by the smallest
 shape that reaches it.  One table per entry point; every row DECLARES the plan it is meant to reach and the test asserts that
 hip_ops.gn_last_plan() -- the record the launcher writes just before it launches -- equals the declaration, so a row that
-drifts to another kernel fails the TABLE.  tests/test_gn_plans_cpu.py holds the written enumeration these tables must cover.
+drifts to another kernel fails the TABLE, and equals what the plan query (hip_ops.gn_fwd_plan / gn_bwd_plan) answers for the
+arguments of that launch.  tests/test_gn_plans_cpu.py holds the written enumeration these tables must cover.
 
 Every case
   1. calls the C ABI through _lib.call on buffers the test owns,
@@ -373,9 +374,13 @@ def _stream():
     return hip_ops._stream()
 
 
-def last_plan():
+def last_plan(query, *args, **kw):
+    """The record of the launch just made, which must be what the plan query (hip_ops.gn_fwd_plan / gn_bwd_plan) answers for the
+    arguments of that launch."""
     from genesis_amd import hip_ops
-    return hip_ops.gn_last_plan()
+    got, would = hip_ops.gn_last_plan(), getattr(hip_ops, query)(*args, **kw)
+    assert got == would, (query, args, kw, got, would)
+    return got
 
 
 def dview(v):
@@ -394,7 +399,7 @@ def run_fwd(r, y, gamma, beta, d0, d1, parts=None):
     else:
         slabs, nsplit, stride, bias, ysum = parts
         _lib.call('gx_gn_relu_fwd_parts', ptr(slabs), nsplit, stride, ptr(bias), ptr(ysum), *tail)
-    return mean, rstd, last_plan()
+    return mean, rstd, last_plan('gn_fwd_plan', N, C, H, W, groups, 1 if parts is None else parts[1])
 
 
 def nan_workspace(nbytes):
@@ -417,7 +422,8 @@ def run_bwd(r, y, gamma, beta, mean, rstd, s0, s1=None):
         return [ptr(s[0]), int(ctot), int(s[1]), int(s[2]), int(s[3]), int(s[4])]
     _lib.call('gx_gn_relu_bwd_parts', ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), N, C, H, W, groups, *src(s0), *src(s1),
               ptr(dy), ptr(dg), ptr(db), ptr(dbias), ptr(ws), nb, _stream())
-    return dy, dg, db, dbias, last_plan()
+    return dy, dg, db, dbias, last_plan('gn_bwd_plan', N, C, H, W, groups, g0_mode=s0[2], g0_ctot=src(s0)[1], g0_nsplit=s0[3],
+                                        g1_nsplit=s1[3] if s1 else 0, ws_bytes=nb)
 
 
 def check_grads(r, got, ref, ref32, what, dy_rtol=1e-4, dy_atol=1e-5):
@@ -633,7 +639,7 @@ def test_projected_backward_row(r, wp):
     ops = [dev(inp['y']), dev(inp['gamma']), dev(inp['beta']), dev(mref), dev(rref), dev(g_out), dev(w), None if gate is None else dev(gate)]
     _lib.call('gx_gn_relu_bwd_proj', *[ptr(t) for t in ops[:5]], N, C, H, W, groups, ptr(ops[5]), Cout, ptr(ops[6]), ptr(ops[7]),
               ptr(dy), ptr(dg), ptr(db), ptr(dbias), ptr(wpart), ptr(bpart), ptr(ws), nb, _stream())
-    got = last_plan()
+    got = last_plan('gn_bwd_plan', N, C, H, W, groups, g0_mode=3, g0_ctot=Cout, g0_nsplit=0, want_wpart=wp, ws_bytes=nb)
     assert got == proj_plan(r, wp), (got, proj_plan(r, wp))
     check_grads(r, (dy, dg, db, dbias), ref, ref32, r['id'])
     if wp:
