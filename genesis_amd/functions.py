@@ -1390,8 +1390,10 @@ class LinearFn(torch.autograd.Function):
         x2, y = ctx.saved_tensors
         w, b = ctx.params
         g2 = g.contiguous().view(-1, w.shape[0])
-        need_w = ctx.needs_input_grad[1]
-        ow, acc_w = _gout_acc(w) if need_w else (None, False)
+        want_w = ctx.needs_input_grad[1]
+        # (the kernels produce db together with dw: a trainable bias on a frozen weight still takes the dw launch)
+        need_w = want_w or (b is not None and ctx.needs_input_grad[2])
+        ow, acc_w = _gout_acc(w) if want_w else (None, False)
         ob, acc_b = _gout_acc(b) if (need_w and b is not None) else (None, acc_w)
         if acc_w != acc_b or (ow is None) != (ob is None and b is not None):
             # (a weight and its bias always travel together; anything else goes the plain way)
@@ -1403,7 +1405,7 @@ class LinearFn(torch.autograd.Function):
                                     accumulate_dw=acc_w)
         if dw is not None and ow is None:
             dw = dw.view(w.shape)
-        return (dx.view(ctx.xshape) if dx is not None else None, _ret(ow, dw) if need_w else None,
+        return (dx.view(ctx.xshape) if dx is not None else None, _ret(ow, dw) if want_w else None,
                 _ret(ob, db) if (b is not None and need_w) else None, None)
 
 
